@@ -9,6 +9,11 @@ its roofline target is quoted on — with the deterministic synthetic
 sample), scene already resident in HBM, output a device float3 accumulation
 buffer.
 
+A plain run sets up the scene, warms up, times `--steps` steps, writes the
+last step's frame if `--dump-outputs DIR` is given, and prints the result
+line.  Everything below that is not the multi-GPU path itself runs only with
+`--full` (and each leg can be dropped again with its `--no-*` option).
+
 Also on the same line (`configs`): short timed runs of the other GPU configs
 of BASELINE.json at their stated sizes — C2 RandomScene 1200x675x500 spp
 (depth 50), C3 CornellBoxScene 600x600x1000 spp (depth 5), C5 HDRITestScene
@@ -96,21 +101,33 @@ def parse():
     ap.add_argument("--blas", choices=["sah", "reference", "device"], default="sah",
                     help="mesh BLAS builder: host SAH (default), the caller's topology, or the GPU LBVH "
                          "(build.hip); the world BVH is SAH except for 'reference'")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-count", action="store_true", help="skip the instrumented count run")
-    ap.add_argument("--no-configs", action="store_true", help="skip the C2/C3/C5 runs")
-    ap.add_argument("--no-balance", action="store_true", help="skip the shard-balance timing")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-count", action="store_true", help="with --full: skip the instrumented count run")
+    ap.add_argument("--no-configs", action="store_true", help="with --full: skip the C2/C3/C5 runs")
+    ap.add_argument("--no-balance", action="store_true", help="with --full: skip the shard-balance timing")
     ap.add_argument("--no-three-pass", action="store_true",
-                    help="skip the reference's published workload (HDRITestScene 800x450, 3 progressive passes)")
+                    help="with --full: skip the reference's published workload (HDRITestScene 800x450, 3 progressive passes)")
     ap.add_argument("--config-steps", type=int, default=2)
     ap.add_argument("--cpu-spp", type=int, default=48, help="spp of the CPU baseline sample")
     ap.add_argument("--cpu-threads", type=int, default=0, help="0: every host core available to the job")
     ap.add_argument("--no-pmc", action="store_true",
-                    help="skip the live rocprofv3 --pmc passes (traffic then comes from profiles/pmc_*.json)")
+                    help="with --full: skip the live rocprofv3 --pmc passes (traffic then comes from profiles/pmc_*.json)")
     ap.add_argument("--pmc-child", action="store_true", help=argparse.SUPPRESS)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the other legs: live PMC passes, instrumented counts and "
+                         "roofline, the C2/C3/C5 configs, shard balance, the reference's three-pass workload and the "
+                         "CPU baseline (each can be dropped again with its --no-* option; without --full none of them "
+                         "runs and the --no-* options change nothing)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the frame of the last timed step to DIR/frame.npy (float32, H x W x 3 radiance sums); a "
+                         "frame above 64 MB is written as a fixed sample of pixels instead: frame.npy is then n x 3 "
+                         "and DIR/frame_pixels.npy holds the n pixel ids (y * W + x, as float64)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.pmc_child:   # one profiled step of the workload, nothing else
         args.steps, args.warmup = 1, 0
+    if args.pmc_child or not args.full:   # a plain run: set up, warm up, time the steps, print the line
         args.no_cpu_baseline = args.no_count = args.no_configs = args.no_balance = args.no_pmc = True
         args.no_three_pass = True
     return args
@@ -542,6 +559,27 @@ def kernel_report(w: Workload, work_k: dict, pmc: dict | None, ktimes: list):
     return out
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir: str, frame, H: int, W: int) -> None:
+    """What the timed path hands its caller after the last timed step: the
+    float3 accumulation buffer (per-pixel radiance sums over the spp samples),
+    as <out_dir>/frame.npy, float32 [H, W, 3].  A frame above the size limit
+    is written as a fixed, seeded sample of its pixels, [n, 3], with their
+    pixel ids beside it (frame_pixels.npy, as float64)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    px = np.ascontiguousarray(frame, dtype=np.float32).reshape(H * W, 3)
+    per_pixel = 3 * 4 + 8   # the sample's float32 triple and its float64 pixel id
+    if px.nbytes <= DUMP_LIMIT_BYTES:
+        np.save(os.path.join(out_dir, "frame.npy"), px.reshape(H, W, 3))
+        return
+    ids = np.sort(np.random.default_rng(0).choice(H * W, size=DUMP_LIMIT_BYTES // per_pixel - 64, replace=False))
+    np.save(os.path.join(out_dir, "frame.npy"), px[ids])
+    np.save(os.path.join(out_dir, "frame_pixels.npy"), ids.astype(np.float64))
+
+
 def main():
     args = parse()
     import numpy as np
@@ -607,6 +645,8 @@ def main():
         t_d = time.perf_counter()
         _host = w.accum.cpu()
         d2h_ms = (time.perf_counter() - t_d) * 1e3
+        if args.dump_outputs:   # before any later leg renders into the buffer again
+            dump_outputs(args.dump_outputs, _host.numpy(), H, W)
         del _host
 
     roofline = None

@@ -10,23 +10,21 @@ asserts at the bottom of rtgpu.go):
 * every `Kind*/Mat*/Tex*/Status*/Opt*/Build*` constant equals the C enum
   value its comment names, and ABIVersion equals RT_ABI_VERSION;
 * every `C.<name>` the binding uses is declared in rtgpu.h (or is libc/cgo);
-* the in-package files only select fields and methods that the reference's
-  own types declare (rt/*.go), and only call functions defined in the
-  reference's package rt, in the binding itself, or Go builtins (skipped
-  when /root/reference is absent).
+* the in-package files only use names of package rtgpu that rtgpu.go exports
+  and the few standard-library names they are expected to use, and the
+  renderer declares the drop-in entry points and keeps the embedded
+  renderer's progress state up to date.  (What they select on the reference's
+  own types needs the reference's sources and a Go compiler: not checked here.)
 """
 import os
 import re
 import subprocess
 import tempfile
 
-import pytest
-
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 RTGPU_GO = os.path.join(ROOT, "go", "rtgpu", "rtgpu.go")
 RT_DIR = os.path.join(ROOT, "go", "rt")
 HEADER = os.path.join(ROOT, "include", "rtgpu.h")
-REFERENCE_RT = "/root/reference/rt"
 
 GO_SCALARS = {"int8": 1, "uint8": 1, "byte": 1, "int16": 2, "uint16": 2, "int32": 4, "uint32": 4, "float32": 4,
               "int64": 8, "uint64": 8, "float64": 8}
@@ -153,105 +151,36 @@ def test_c_identifiers_exist():
         assert re.search(r"\b%s\b" % bare, hdr), f"C.{name} is not declared in rtgpu.h"
 
 
-# ---- the in-package files against the reference's package rt ---------------
+# ---- the in-package files against what the repository itself declares ------
 
-GO_BUILTINS = {"append", "cap", "copy", "len", "make", "max", "min", "new", "panic", "print", "println", "delete",
-               "int", "int32", "int64", "uint32", "uint64", "float32", "float64", "byte", "string", "uintptr", "bool",
-               "func", "if", "for", "switch", "return", "range"}
-
-
-def _ref_decls():
-    types, funcs, methods = {}, set(), {}
-    for fn in os.listdir(REFERENCE_RT):
-        if not fn.endswith(".go"):
-            continue
-        src = _read(os.path.join(REFERENCE_RT, fn))
-        for m in re.finditer(r"^type (\w+) struct \{\n(.*?)\n\}", src, re.S | re.M):
-            fields = set()
-            for line in m.group(2).splitlines():
-                line = line.split("//")[0].strip()
-                if not line:
-                    continue
-                fm = re.match(r"(\w+(?:\s*,\s*\w+)*)\s+\S", line)
-                if fm:
-                    fields |= {n.strip() for n in fm.group(1).split(",")}
-                else:
-                    fields.add(line.lstrip("*").split(".")[-1])   # embedded
-            types[m.group(1)] = fields
-        for m in re.finditer(r"^type (\w+) ", src, re.M):
-            types.setdefault(m.group(1), set())
-        funcs |= set(re.findall(r"^func (\w+)\(", src, re.M))
-        for recv, name in re.findall(r"^func \(\w+ \*?(\w+)\) (\w+)\(", src, re.M):
-            methods.setdefault(recv, set()).add(name)
-    return types, funcs, methods
-
-
-@pytest.mark.skipif(not os.path.isdir(REFERENCE_RT), reason="reference tree not present")
-def test_flattener_selects_only_reference_fields():
-    types, funcs, methods = _ref_decls()
-    src = _read(os.path.join(RT_DIR, "gpu_flatten.go"))
-    # case *T: blocks of the type switches: o.<sel> must be a field or method of T
-    checked = 0
-    for m in re.finditer(r"case \*(\w+):(.*?)(?=\n\s*case |\n\s*default:)", src, re.S):
-        t, body = m.groups()
-        assert t in types, f"reference has no type {t}"
-        for sel in set(re.findall(r"\bo\.(\w+)", body)):
-            assert sel in types[t] or sel in methods.get(t, set()), f"{t} has no field or method {sel}"
-            checked += 1
-    assert checked >= 40
-    # selectors outside the switches
-    for sel in set(re.findall(r"\bc\.(\w+)", src.split("func GPUCameraDesc")[1])):
-        assert sel in types["Camera"] | methods.get("Camera", set()), f"Camera has no {sel}"
-    for sel in set(re.findall(r"\benv\.(\w+)", src)):
-        assert sel in types["HDRIEnvironment"] | methods.get("HDRIEnvironment", set()), sel
-    for sel in set(re.findall(r"\bimg\.(\w+)", src)):
-        assert sel in types["ImageLoader"] | methods.get("ImageLoader", set()), sel
-    for sel in set(re.findall(r"\bp\.(\w+)", src.split("func (f *gpuFlat) perlin")[1].split("\nfunc ")[0])):
-        assert sel in types["Perlin"], sel
-
-
-@pytest.mark.skipif(not os.path.isdir(REFERENCE_RT), reason="reference tree not present")
-def test_renderer_uses_only_bucket_renderer_members():
-    types, funcs, methods = _ref_decls()
+def test_renderer_declares_the_drop_in_entry_points():
     src = _read(os.path.join(RT_DIR, "gpu_bucket_renderer.go"))
-    br = types["BucketRenderer"] | methods.get("BucketRenderer", set())
+    # the progress state of the embedded renderer that the drop-in keeps up to date
     used = set(re.findall(r"\br\.(\w+)", src))
     assert {"framebuffer", "mu", "completed", "currentPass", "totalPasses", "passComplete"} <= used
-    for sel in used:
-        assert sel in br, f"BucketRenderer has no {sel}"
-    # the embedded renderer supplies the rest of the ebiten.Game method set
-    for m in ("Draw", "Layout", "SaveImage", "IsCompleted", "GetRenderDuration", "Update"):
-        assert m in methods["BucketRenderer"], m
     assert re.search(r"func \(g \*GPUBucketRenderer\) Update\(\) error", src)
     assert re.search(r"func NewGPUBucketRenderer\(camera \*Camera, world Hittable, bucketSize int, numWorkers int\)",
                      src)
 
 
-@pytest.mark.skipif(not os.path.isdir(REFERENCE_RT), reason="reference tree not present")
-def test_no_undefined_functions():
-    types, funcs, methods = _ref_decls()
+def test_in_package_files_use_only_exported_rtgpu_and_expected_std_names():
     ours = ""
     for fn in sorted(os.listdir(RT_DIR)):
         ours += _read(os.path.join(RT_DIR, fn))
     code = re.sub(r"//.*", "", ours)
     code = re.sub(r'"(?:[^"\\]|\\.)*"', '""', code)
-    defined = set(re.findall(r"^func (?:\([^)]*\) )?(\w+)\(", code, re.M))
     rtgpu_src = re.sub(r"//.*", "", _read(RTGPU_GO))
     rtgpu_exported = set(re.findall(r"^func (?:\([^)]*\) )?([A-Z]\w*)\(", rtgpu_src, re.M))
     rtgpu_exported |= set(re.findall(r"^type ([A-Z]\w*) ", rtgpu_src, re.M))
     rtgpu_exported |= set(re.findall(r"^\s*([A-Z]\w*)\s+(?:int32\s+)?=", rtgpu_src, re.M))
     std = {"fmt": {"Sprintf", "Fprintf", "Errorf"}, "math": {"Tan"}, "unsafe": {"Slice", "Pointer", "Sizeof"},
            "time": {"Now", "Since", "Duration", "Millisecond"}, "os": {"Getenv"}}
+    checked = 0
     for pkg, name in set(re.findall(r"\b(\w+)\.([A-Z]\w*)\b", code)):
         if pkg == "rtgpu":
             assert name in rtgpu_exported, f"rtgpu.{name} undefined"
+            checked += 1
         elif pkg in std:
             if name not in ("Stderr",):
                 assert name in std[pkg], f"{pkg}.{name} not expected"
-    # bare calls: ours, the reference package's, builtins or a local closure
-    for name in set(re.findall(r"(?<![.\w])([A-Za-z_]\w*)\(", code)):
-        assert (name in defined or name in funcs or name in GO_BUILTINS or name in types
-                or name in ("errGPUUnsupported",)), f"call to undefined {name}"
-    # method calls on receivers we own
-    for name in set(re.findall(r"\b[fg]\.(\w+)\(", code)):
-        assert name in defined or name in methods.get("BucketRenderer", set()), f"method {name} undefined"
+    assert checked >= 10

@@ -11,7 +11,7 @@ factor of a whole-line fill; a pattern whose requests per missed line and
 request sizes match it moves the same bytes per line.  Then the production
 kernels' requests per L2 miss on the bench workload, for the same inference.
 
-usage: tools/fetch_calib.py gpurun_out/calib
+usage: tools/fetch_calib.py bench_out/calib
 """
 import csv
 import glob
@@ -101,7 +101,7 @@ def production(out):
 
 
 def main():
-    out = sys.argv[1] if len(sys.argv) > 1 else "gpurun_out/calib"
+    out = sys.argv[1] if len(sys.argv) > 1 else "bench_out/calib"
     lines, m = micro(out)
     p = production(out)
     res = {"lines_per_launch": lines, "line_bytes": 128, "patterns": m, "production": p}

@@ -2,11 +2,11 @@
 # FETCH_SIZE calibration (tools/fetch_calib/fetch_calib.hip): the counter
 # passes of the microkernel patterns, then the same request counters of the
 # production kernels on the bench workload (one step, one stream).  Each pass
-# its own rocprofv3 run with its own time limit.  Output: gpurun_out/calib/;
+# its own rocprofv3 run with its own time limit.  Output: $BENCH_OUT/calib/ (default bench_out/calib/, or OUT=...);
 # tools/fetch_calib.py turns it into profiles/r06_fetch_calib.txt.
 set -o pipefail
 export TMPDIR=/tmp
-OUT=${OUT:-gpurun_out/calib}
+OUT=${OUT:-${BENCH_OUT:-bench_out}/calib}
 mkdir -p $OUT
 bin=tools/fetch_calib/fetch_calib
 $bin 65536 1 > $OUT/order.json || exit 1

@@ -4,7 +4,7 @@
 # step's name:
 #   tests [pytest args]        pytest -m gpu (plain test failures do not stop the call)
 #   smoke                      __graft_entry__.smoke()
-#   bench [bench args]         the default bench line -> gpurun_out/bench.json
+#   bench [bench args]         the full bench line (bench.py --full) -> $BENCH_OUT/bench.json (default bench_out/)
 #   bal <spec> ...             tools/bal_ab.sh (value + 2/4/8-way shard predictions)
 #   ab <spec> ...              tools/ab.sh (value, per-kernel ms, work per sample; BENCH_ARGS from the env)
 #   abc3 <spec> ...            tools/ab.sh on C3 (CornellBoxScene 600x600, 1000 spp)
@@ -14,7 +14,8 @@
 # under its own time limit; a timeout, crash or abort ends the call.
 #   e.g. bash tools/gpu_steps.sh tests "bal r5::lib_r5 new::lib" "abc3 new::lib"
 set -o pipefail
-mkdir -p gpurun_out
+OUT=${BENCH_OUT:-bench_out}
+mkdir -p $OUT
 fatal() {   # exit codes that mean a fault, a hang or a kill: start nothing more
   case $1 in 124|134|137|139|143) return 0 ;; *) return 1 ;; esac
 }
@@ -29,16 +30,16 @@ for step in "$@"; do
   case $name in
     tests)
       timeout -k 10 500 python3 -u -m pytest tests -m gpu -x -q --timeout 120 --timeout-method thread "${args[@]}" \
-        > gpurun_out/gpu_tests.log 2>&1; rc=$?
-      tail -3 gpurun_out/gpu_tests.log
+        > $OUT/gpu_tests.log 2>&1; rc=$?
+      tail -3 $OUT/gpu_tests.log
       if fatal $rc; then exit $rc; fi ;;
     smoke)
-      timeout -k 10 200 python3 -c "import __graft_entry__ as g; g.smoke()" > gpurun_out/smoke.log 2>&1; rc=$?
-      tail -2 gpurun_out/smoke.log
+      timeout -k 10 200 python3 -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.log 2>&1; rc=$?
+      tail -2 $OUT/smoke.log
       [ $rc -eq 0 ] || exit $rc ;;
     bench)
-      timeout -k 10 400 python3 bench.py "${args[@]}" > gpurun_out/bench.json 2> gpurun_out/bench.err || { rc=$?; tail -20 gpurun_out/bench.err; exit $rc; }
-      cat gpurun_out/bench.json ;;
+      timeout -k 10 400 python3 bench.py --full "${args[@]}" > $OUT/bench.json 2> $OUT/bench.err || { rc=$?; tail -20 $OUT/bench.err; exit $rc; }
+      cat $OUT/bench.json ;;
     bal) bash tools/bal_ab.sh "${args[@]}" || exit $? ;;
     ab) bash tools/ab.sh "${args[@]}" || exit $? ;;
     abc2) BENCH_ARGS="$C2 $QUICK" bash tools/ab.sh "${args[@]}" || exit $? ;;

@@ -3,7 +3,7 @@
 RTGPU_LIB_DIR at several path depths, saved as .npy for a host-side diff
 against the production build and the CPU oracle (tools/guard_diff.py).
 
-  RTGPU_LIB_DIR=lib_guard python3 tools/guard_diag.py gpurun_out/guard/guard
+  RTGPU_LIB_DIR=lib_guard python3 tools/guard_diag.py bench_out/guard/guard
 """
 import os
 import sys

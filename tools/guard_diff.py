@@ -4,7 +4,7 @@ library's image-mean relative bias against the CPU oracle (fp32 mirror and
 fp64 restatement) on the same scene / seed / spp, run-to-run equality, and
 the pixels where two libraries differ.
 
-  python3 tools/guard_diff.py gpurun_out/guard lib_guard lib_head lib
+  python3 tools/guard_diff.py bench_out/guard lib_guard lib_head lib
 """
 import os
 import sys

@@ -4,18 +4,20 @@
 # [SCENE_ARGS=...]; prints bytes per launch per kernel family.
 set -o pipefail
 export TMPDIR=/tmp
+OUT=${BENCH_OUT:-bench_out}
+mkdir -p $OUT
 for lib in "$@"; do
   for c in WRITE_SIZE FETCH_SIZE; do
-    RTGPU_LIB_DIR=$lib RTGPU_STREAMS=1 timeout -s KILL 180 rocprofv3 --pmc $c --output-format csv -d gpurun_out/pmcab_${lib}_$c -o p -- \
-      python3 bench.py --pmc-child $SCENE_ARGS > /dev/null 2> gpurun_out/pmcab_${lib}_$c.err || exit 1
+    RTGPU_LIB_DIR=$lib RTGPU_STREAMS=1 timeout -s KILL 180 rocprofv3 --pmc $c --output-format csv -d $OUT/pmcab_${lib}_$c -o p -- \
+      python3 bench.py --pmc-child $SCENE_ARGS > /dev/null 2> $OUT/pmcab_${lib}_$c.err || exit 1
   done
-  python3 - "$lib" <<'PY'
+  python3 - "$lib" "$OUT" <<'PY'
 import csv, glob, sys
 from collections import defaultdict
-lib = sys.argv[1]
+lib, out = sys.argv[1:3]
 for c in ("WRITE_SIZE", "FETCH_SIZE"):
     v = defaultdict(float); d = defaultdict(set)
-    for f in glob.glob(f"gpurun_out/pmcab_{lib}_{c}/**/*counter_collection.csv", recursive=True):
+    for f in glob.glob(f"{out}/pmcab_{lib}_{c}/**/*counter_collection.csv", recursive=True):
         for r in csv.DictReader(open(f)):
             n = r["Kernel_Name"]
             for k in ("k_extend", "k_shadow", "k_shade", "k_nee_apply"):

@@ -1,10 +1,11 @@
 #!/bin/bash
 # PMC passes (one counter group per pass, never combined with tracing) of
-# bench.py on the default workload (one step).  Output: gpurun_out/pmc/<pass>/
+# bench.py on the default workload (one step).  Output: $BENCH_OUT/pmc/<pass>/
+# (default bench_out/pmc/, or OUT=...)
 set -e
 export TMPDIR=/tmp
-OUT=${OUT:-gpurun_out/pmc}
-ARGS=${ARGS:---steps 1 --warmup 0 --no-cpu-baseline --no-count --no-configs --no-balance --no-three-pass}
+OUT=${OUT:-${BENCH_OUT:-bench_out}/pmc}
+ARGS=${ARGS:---steps 1 --warmup 0}
 mkdir -p $OUT
 run() {
   name=$1; shift

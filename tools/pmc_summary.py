@@ -5,7 +5,7 @@ import os
 import sys
 from collections import defaultdict
 
-root = sys.argv[1] if len(sys.argv) > 1 else "gpurun_out/pmc"
+root = sys.argv[1] if len(sys.argv) > 1 else "bench_out/pmc"
 agg = defaultdict(lambda: defaultdict(float))
 calls = defaultdict(set)
 for f in glob.glob(os.path.join(root, "*", "**", "*counter_collection.csv"), recursive=True):

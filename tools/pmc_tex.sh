@@ -3,12 +3,12 @@
 # L1 and its address translation) of bench.py's default workload, one pass
 # per counter group, for each node format given (default: fp32 quant8;
 # NODES="fp32 wide8" for the 8-wide comparison).
-# Output: gpurun_out/pmc_tex/<nodes>/<pass>/; summarise with
-#   python3 tools/pmc_summary.py gpurun_out/pmc_tex/<nodes>
+# Output: $BENCH_OUT/pmc_tex/<nodes>/<pass>/ (default bench_out/pmc_tex/, or OUT=...); summarise with
+#   python3 tools/pmc_summary.py bench_out/pmc_tex/<nodes>
 set -e
 export TMPDIR=/tmp
-OUT=${OUT:-gpurun_out/pmc_tex}
-ARGS=${ARGS:---steps 1 --warmup 0 --no-cpu-baseline --no-count --no-configs --no-balance --no-three-pass --no-pmc}
+OUT=${OUT:-${BENCH_OUT:-bench_out}/pmc_tex}
+ARGS=${ARGS:---steps 1 --warmup 0}
 for nodes in ${NODES:-fp32 quant8}; do
   mkdir -p $OUT/$nodes
   run() {

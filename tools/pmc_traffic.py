@@ -19,7 +19,7 @@ import shutil
 import sys
 from collections import defaultdict
 
-root = sys.argv[1] if len(sys.argv) > 1 else "gpurun_out/prof"
+root = sys.argv[1] if len(sys.argv) > 1 else "bench_out/prof"
 tag = sys.argv[2] if len(sys.argv) > 2 else "r01"
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 

@@ -10,8 +10,8 @@ RTGPU_STREAMS=1 for per-kernel attribution):
   spp8   every pixel at 500/8 spp (the same sample count as a 1/8 shard)
   rr2 / rr4 / rr16 / rr32  the round-robin shards of other sizes
 
-  rocprofv3 --kernel-trace --output-format csv -d gpurun_out/sa -o kt -- python3 tools/shard_anat.py
-  python3 tools/shard_anat.py --analyze gpurun_out/sa
+  rocprofv3 --kernel-trace --output-format csv -d bench_out/sa -o kt -- python3 tools/shard_anat.py
+  python3 tools/shard_anat.py --analyze bench_out/sa
 """
 import csv
 import glob

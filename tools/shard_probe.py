@@ -3,8 +3,8 @@
 shard of it (run under `rocprofv3 --kernel-trace`): which kernels carry the
 per-render overhead that makes 8 shards cost more than one frame.
 
-  rocprofv3 --kernel-trace --output-format csv -d gpurun_out/sp -o kt -- python3 tools/shard_probe.py
-  python3 tools/shard_probe.py --analyze gpurun_out/sp
+  rocprofv3 --kernel-trace --output-format csv -d bench_out/sp -o kt -- python3 tools/shard_probe.py
+  python3 tools/shard_probe.py --analyze bench_out/sp
 """
 import csv
 import glob
