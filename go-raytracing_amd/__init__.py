@@ -118,6 +118,11 @@ class RtStats(C.Structure):
     _fields_ = [("kernel_ms", C.c_double), ("samples", C.c_uint64)]
 
 
+class RtDenoiseParams(C.Structure):
+    _fields_ = [("iterations", C.c_int32), ("normal_power_log2", C.c_int32), ("demodulate", C.c_int32),
+                ("sigma_color", C.c_float), ("sigma_depth", C.c_float), ("albedo_eps", C.c_float)]
+
+
 class RtWorkCounts(C.Structure):
     _fields_ = [(n, C.c_uint64) for n in ("samples", "rays", "shadow_rays", "node_visits", "sphere_tests",
                                           "quad_tests", "tri_tests", "plane_tests", "instance_visits",
@@ -207,6 +212,14 @@ def rtgpu() -> C.CDLL:
             lib.rt_extend_hits.argtypes = [P, C.POINTER(RtCameraDesc), U32, I32, I32, C.POINTER(I32), C.POINTER(I32),
                                            C.POINTER(C.c_float), C.POINTER(C.c_float)]
             lib.rt_shadow_visibility.argtypes = [P, C.POINTER(RtCameraDesc), U32, I32, I32, C.POINTER(I32)]
+        if hasattr(lib, "rt_render_features"):
+            lib.rt_render_features.argtypes = [P, C.POINTER(RtCameraDesc), C.POINTER(RtRenderParams),
+                                               C.POINTER(C.c_float), C.POINTER(RtStats)]
+            lib.rt_render_features_device.argtypes = [P, C.POINTER(RtCameraDesc), C.POINTER(RtRenderParams), P, P]
+            lib.rt_denoise_default_params.argtypes = [C.POINTER(RtDenoiseParams)]
+            lib.rt_denoise.argtypes = [P, C.POINTER(C.c_float), C.POINTER(C.c_float), I32, I32, I32,
+                                       C.POINTER(RtDenoiseParams), C.POINTER(C.c_float)]
+            lib.rt_denoise_device.argtypes = [P, P, P, I32, I32, I32, C.POINTER(RtDenoiseParams), P, P]
         _rtgpu = lib
     return _rtgpu
 
@@ -392,6 +405,20 @@ def make_params(spp: int, depth: int, seed: int = 1, sample_offset: int = 0, buc
     return p
 
 
+def denoise_params(**overrides) -> RtDenoiseParams:
+    """rt_denoise_default_params with keyword overrides (iterations,
+    normal_power_log2, demodulate, sigma_color, sigma_depth, albedo_eps)."""
+    dp = RtDenoiseParams()
+    rc = rtgpu().rt_denoise_default_params(C.byref(dp))
+    if rc != RT_OK:
+        raise RTError(rc, "rt_denoise_default_params failed")
+    for k, v in overrides.items():
+        if k not in dict(RtDenoiseParams._fields_):
+            raise TypeError(f"unknown denoise parameter {k!r}")
+        setattr(dp, k, v)
+    return dp
+
+
 # ---------------------------------------------------------------------------
 # GPU context (rt_ctx)
 # ---------------------------------------------------------------------------
@@ -489,6 +516,38 @@ class Context:
     def render_device(self, camera: RtCameraDesc, params: RtRenderParams, dev_ptr: int, stream: int = 0):
         self._check(self._lib.rt_render_device(self._h, C.byref(camera), C.byref(params), C.c_void_p(dev_ptr),
                                                C.c_void_p(stream)))
+
+    def render_features(self, camera: RtCameraDesc, params: RtRenderParams, feat: Optional[np.ndarray] = None):
+        """Feature buffers (rt_render_features): (H, W, 8) float32 sums over the
+        call's samples of albedo.rgb, normal.xyz, depth, coverage at the camera
+        rays' closest hits (the same path keys as render()), and the stats."""
+        if feat is None:
+            feat = np.zeros((camera.image_height, camera.image_width, 8), np.float32)
+        st = RtStats()
+        self._check(self._lib.rt_render_features(self._h, C.byref(camera), C.byref(params), _f32p(feat),
+                                                 C.byref(st)))
+        return feat, st
+
+    def render_features_device(self, camera: RtCameraDesc, params: RtRenderParams, dev_ptr: int, stream: int = 0):
+        self._check(self._lib.rt_render_features_device(self._h, C.byref(camera), C.byref(params),
+                                                        C.c_void_p(dev_ptr), C.c_void_p(stream)))
+
+    def denoise(self, accum: np.ndarray, feat: np.ndarray, spp: int, **params) -> np.ndarray:
+        """rt_denoise: the a-trous filter over (H, W, 3) radiance sums guided by
+        the (H, W, 8) feature sums of the same `spp` samples; returns filtered
+        sums.  Keyword arguments override denoise_params()'s defaults."""
+        h, w = accum.shape[:2]
+        out = np.zeros((h, w, 3), np.float32)
+        dp = denoise_params(**params)
+        self._check(self._lib.rt_denoise(self._h, _f32p(accum), _f32p(feat), w, h, spp, C.byref(dp), _f32p(out)))
+        return out
+
+    def denoise_device(self, accum_ptr: int, feat_ptr: int, width: int, height: int, spp: int, out_ptr: int,
+                       stream: int = 0, **params):
+        """rt_denoise_device: the same over device arrays, asynchronous on `stream`."""
+        dp = denoise_params(**params)
+        self._check(self._lib.rt_denoise_device(self._h, C.c_void_p(accum_ptr), C.c_void_p(feat_ptr), width, height,
+                                                spp, C.byref(dp), C.c_void_p(out_ptr), C.c_void_p(stream)))
 
     def sync(self) -> None:
         """Wait for every enqueued render; raises RTError(RT_ERR_DEVICE) on a device error."""

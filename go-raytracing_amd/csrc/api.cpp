@@ -22,6 +22,7 @@
 #include "flatten.h"
 #include "probe.h"
 #include "wavefront.h"
+#include "denoise.h"
 
 using namespace rtg;
 
@@ -70,6 +71,13 @@ struct rt_ctx {
   int opt_blocks = 0;
   int opt_tail = 0;                     // RT_OPT_TAIL: 0 automatic, 1 off, > 1 the rays-left threshold
   bool probing = false;                 // path_probe: every bounce through the wavefront kernels
+  // rt_render_features: the render path in its feature mode (WavePlan::feat_acc);
+  // wfacc = 8 fp64 sums per listed pixel, feat = the host variant's device image
+  bool feat_mode = false;
+  DevBuf wfacc, feat;
+  // rt_denoise: the guide image and the two ping-pong images (one allocation),
+  // and the host variant's device copies of its arrays
+  DevBuf dn_work, dn_in, dn_feat, dn_out;
   int opt_streams = 0;            // RT_OPT_STREAMS: 1..kMaxTwins twins (0 = automatic: kDefaultTwins)
   int opt_overlap = 0;            // RT_OPT_OVERLAP: 0 automatic, 1 off, 2 on
   // bounce overlap (WavePlan::overlap): each twin's k_shadow / k_nee_apply
@@ -419,6 +427,7 @@ int render_wave(rt_ctx* ctx, const DCamera& dc, const rt_render_params* p, const
   }
   if ((rc = ensure(ctx, ctx->wpix, npix * sizeof(uint32_t)))) return rc;
   if ((rc = ensure(ctx, ctx->wacc, size_t(npix) * 3 * sizeof(double)))) return rc;
+  if (ctx->feat_mode && (rc = ensure(ctx, ctx->wfacc, size_t(npix) * kFeatFloats * sizeof(double)))) return rc;
   if ((rc = ensure(ctx, ctx->counters, CNT_WORDS * sizeof(unsigned long long)))) return rc;
   // pixel list through pinned staging (async-safe)
   HIPCHK(hipEventSynchronize(ctx->pix_ev));
@@ -463,6 +472,7 @@ int render_wave(rt_ctx* ctx, const DCamera& dc, const rt_render_params* p, const
   // each twin: slot_f4 arrays of its own S_t slots, its queue counters and
   // job words, its slice of the pixel list and the fp64 sums, its spill area
   WaveArgs as[kMaxTwins]{};
+  double* feat_acc[kMaxTwins] = {};   // feature mode: each twin's slice of wfacc
   hipStream_t sts[kMaxTwins] = {st};
   for (int t = 1; t < kMaxTwins; ++t) sts[t] = ctx->twin_st[t - 1];
   float4* fbase = static_cast<float4*>(ctx->wstate.p);
@@ -488,6 +498,7 @@ int render_wave(rt_ctx* ctx, const DCamera& dc, const rt_render_params* p, const
     a.pixels = static_cast<const uint32_t*>(ctx->wpix.p) + pix_off;
     a.npix = twin_npix[t];
     a.acc = static_cast<double*>(ctx->wacc.p) + size_t(pix_off) * 3;
+    if (ctx->feat_mode) feat_acc[t] = static_cast<double*>(ctx->wfacc.p) + size_t(pix_off) * kFeatFloats;
     pix_off += twin_npix[t];
     a.seed = p->seed;
     a.max_depth = p->max_depth;
@@ -514,6 +525,10 @@ int render_wave(rt_ctx* ctx, const DCamera& dc, const rt_render_params* p, const
   plan.samples_per_batch = spb;
   plan.sample_offset = uint32_t(p->sample_offset);
   plan.max_depth = p->max_depth;
+  if (ctx->feat_mode) {   // bounce 0's closest hit only, whatever depth the caller's params name
+    plan.max_depth = 1;
+    plan.feat_acc = feat_acc;
+  }
   plan.num_cus = ctx->num_cus;
   // RTGPU_MAX_BLOCKS (tuning knob, like RTGPU_SLOTS): the option's default
   static const int env_blocks = [] {
@@ -872,6 +887,8 @@ void rt_ctx_destroy(rt_ctx* ctx) {
   if (ctx->err_ev) (void)hipEventDestroy(ctx->err_ev);
   free_buf(ctx->wstate); free_buf(ctx->wq); free_buf(ctx->wpix); free_buf(ctx->wacc);
   free_buf(ctx->wspill);
+  free_buf(ctx->wfacc); free_buf(ctx->feat);
+  free_buf(ctx->dn_work); free_buf(ctx->dn_in); free_buf(ctx->dn_feat); free_buf(ctx->dn_out);
   free_buf(ctx->frame); free_buf(ctx->frame_rgba); free_buf(ctx->frame_buckets);
   if (ctx->pix_pinned) (void)hipHostFree(ctx->pix_pinned);
   if (ctx->probe_pinned) (void)hipHostFree(ctx->probe_pinned);
@@ -1261,6 +1278,124 @@ int rt_render_device(rt_ctx* ctx, const rt_camera_desc* cam, const rt_render_par
   }
   HIPCHK(hipSetDevice(ctx->device));
   return render_multi(ctx, cam, params, accum_rgb_device, st);
+}
+
+// The feature pass (features.hip) through the render path in its feature
+// mode.  A multi-device context runs it on its first device only, like the
+// probes.
+int rt_render_features(rt_ctx* ctx, const rt_camera_desc* cam, const rt_render_params* params, float* feat,
+                       rt_stats* stats) {
+  if (!ctx || !cam || !params || !feat) return RT_ERR_INVALID;
+  HIPCHK(hipSetDevice(ctx->device));
+  if (cam->image_width <= 0 || cam->image_height <= 0) return set_err(ctx, RT_ERR_INVALID, "bad image size");
+  if (!ctx->has_scene) return set_err(ctx, RT_ERR_NO_SCENE, "no scene uploaded");
+  const size_t n = size_t(cam->image_width) * cam->image_height * kFeatFloats;
+  int rc = ensure(ctx, ctx->feat, n * sizeof(float));
+  if (rc) return rc;
+  HIPCHK(hipMemcpyAsync(ctx->feat.p, feat, n * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+  double ms = 0.0;
+  ctx->feat_mode = true;
+  rc = render_impl(ctx, cam, params, static_cast<float*>(ctx->feat.p), ctx->stream, false, nullptr, &ms);
+  ctx->feat_mode = false;
+  if (rc) return rc;
+  HIPCHK(hipMemcpyAsync(feat, ctx->feat.p, n * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  if (stats) {
+    stats->kernel_ms = ms;
+    uint64_t px = 0;
+    if (params->buckets) for (int i = 0; i < params->num_buckets; ++i) px += uint64_t(params->buckets[i].width) * params->buckets[i].height;
+    else px = uint64_t(cam->image_width) * cam->image_height;
+    stats->samples = px * uint64_t(params->samples_per_pixel);
+  }
+  return RT_OK;
+}
+
+int rt_render_features_device(rt_ctx* ctx, const rt_camera_desc* cam, const rt_render_params* params,
+                              float* feat_device, void* hip_stream) {
+  if (!ctx || !cam || !params || !feat_device) return RT_ERR_INVALID;
+  HIPCHK(hipSetDevice(ctx->device));
+  hipStream_t st = hip_stream ? static_cast<hipStream_t>(hip_stream) : ctx->stream;
+  int rc = check_render_error(ctx, false);
+  if (rc) return rc;
+  ctx->feat_mode = true;
+  rc = render_impl(ctx, cam, params, feat_device, st, false, nullptr, nullptr);
+  ctx->feat_mode = false;
+  return rc;
+}
+
+int rt_denoise_default_params(rt_denoise_params* p) {
+  if (!p) return RT_ERR_INVALID;
+  p->iterations = 5;
+  p->normal_power_log2 = 5;
+  p->demodulate = 1;
+  p->sigma_color = 4.0f;
+  p->sigma_depth = 0.1f;
+  p->albedo_eps = 1e-3f;
+  return RT_OK;
+}
+
+// rt_denoise / rt_denoise_device: the passes of denoise.hip on `st` over
+// device arrays, with the context's guide and ping-pong images.
+static int denoise_impl(rt_ctx* ctx, const float* accum, const float* feat, int32_t w, int32_t h, int32_t spp,
+                        const rt_denoise_params* params, float* out, hipStream_t st) {
+  rt_denoise_params dp;
+  rt_denoise_default_params(&dp);
+  if (params) dp = *params;
+  if (w <= 0 || h <= 0 || spp <= 0) return set_err(ctx, RT_ERR_INVALID, "bad image size or samples");
+  if (dp.iterations < 0 || dp.iterations > kDnMaxIterations) return set_err(ctx, RT_ERR_INVALID, "iterations outside 0..8");
+  if (dp.normal_power_log2 < 0 || dp.normal_power_log2 > 16) return set_err(ctx, RT_ERR_INVALID, "normal_power_log2 outside 0..16");
+  if (!(dp.sigma_color > 0.0f) || !(dp.sigma_depth >= 0.0f) || !(dp.albedo_eps > 0.0f))
+    return set_err(ctx, RT_ERR_INVALID, "sigma_color / albedo_eps must be > 0, sigma_depth >= 0");
+  const size_t n = size_t(w) * size_t(h);
+  if (reinterpret_cast<uintptr_t>(feat) % 16 != 0) return set_err(ctx, RT_ERR_INVALID, "feature image not 16-B aligned");
+  {   // the passes read the input while the last one writes the output
+    const char* a0 = reinterpret_cast<const char*>(accum);
+    const char* o0 = reinterpret_cast<const char*>(out);
+    if (a0 < o0 + n * 12 && o0 < a0 + n * 12) return set_err(ctx, RT_ERR_INVALID, "output overlaps the input");
+  }
+  if (dp.iterations == 0) {
+    HIPCHK(hipMemcpyAsync(out, accum, n * 3 * sizeof(float), hipMemcpyDeviceToDevice, st));
+    return RT_OK;
+  }
+  int rc = ensure(ctx, ctx->dn_work, n * 3 * sizeof(float4));
+  if (rc) return rc;
+  DnArgs a{};
+  a.accum = accum; a.feat = feat; a.out = out;
+  a.guide = static_cast<float4*>(ctx->dn_work.p);
+  a.img[0] = a.guide + n; a.img[1] = a.guide + 2 * n;
+  a.w = w; a.h = h; a.spp = float(spp);
+  a.normal_power_log2 = dp.normal_power_log2; a.demodulate = dp.demodulate ? 1 : 0;
+  a.sigma_color = dp.sigma_color; a.sigma_depth = dp.sigma_depth; a.albedo_eps = dp.albedo_eps;
+  HIPCHK(launch_denoise(a, dp.iterations, ctx->num_cus, st));
+  return RT_OK;
+}
+
+int rt_denoise(rt_ctx* ctx, const float* accum_rgb, const float* feat, int32_t width, int32_t height, int32_t spp,
+               const rt_denoise_params* params, float* out_rgb) {
+  if (!ctx || !accum_rgb || !feat || !out_rgb) return RT_ERR_INVALID;
+  HIPCHK(hipSetDevice(ctx->device));
+  if (width <= 0 || height <= 0 || spp <= 0) return set_err(ctx, RT_ERR_INVALID, "bad image size or samples");
+  const size_t n = size_t(width) * size_t(height);
+  int rc;
+  if ((rc = ensure(ctx, ctx->dn_in, n * 3 * sizeof(float)))) return rc;
+  if ((rc = ensure(ctx, ctx->dn_feat, n * kFeatFloats * sizeof(float)))) return rc;
+  if ((rc = ensure(ctx, ctx->dn_out, n * 3 * sizeof(float)))) return rc;
+  HIPCHK(hipMemcpyAsync(ctx->dn_in.p, accum_rgb, n * 3 * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(hipMemcpyAsync(ctx->dn_feat.p, feat, n * kFeatFloats * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+  if ((rc = denoise_impl(ctx, static_cast<const float*>(ctx->dn_in.p), static_cast<const float*>(ctx->dn_feat.p), width,
+                         height, spp, params, static_cast<float*>(ctx->dn_out.p), ctx->stream)))
+    return rc;
+  HIPCHK(hipMemcpyAsync(out_rgb, ctx->dn_out.p, n * 3 * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  return RT_OK;
+}
+
+int rt_denoise_device(rt_ctx* ctx, const float* accum_dev, const float* feat_dev, int32_t width, int32_t height,
+                      int32_t spp, const rt_denoise_params* params, float* out_dev, void* hip_stream) {
+  if (!ctx || !accum_dev || !feat_dev || !out_dev) return RT_ERR_INVALID;
+  HIPCHK(hipSetDevice(ctx->device));
+  hipStream_t st = hip_stream ? static_cast<hipStream_t>(hip_stream) : ctx->stream;
+  return denoise_impl(ctx, accum_dev, feat_dev, width, height, spp, params, out_dev, st);
 }
 
 int rt_sync(rt_ctx* ctx) {

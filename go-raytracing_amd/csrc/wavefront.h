@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "dev_layout.h"
+#include "features.h"   // run_batches' feature mode launches features.hip's kernels
 
 namespace rtg {
 
@@ -111,6 +112,12 @@ struct WavePlan {
   uint8_t* ev_class;
   int max_events;
   int* num_events;
+  // Feature mode (rt_render_features, features.hip): non-null = each batch
+  // runs bounce 0's k_extend only, then k_features on its hit records (into
+  // the unused stream arrays s[0].o / s[0].d: bounce 0 has no stream) and the
+  // feature accumulate; feat_acc[t] holds twin t's 8 fp64 sums per listed
+  // pixel, and launch_wavefront's `out` is the W*H*8 feature image.
+  double* const* feat_acc;
 };
 
 enum : uint8_t { KC_EXTEND = 0, KC_SHADE = 1, KC_SHADOW = 2, KC_OTHER = 3 };

@@ -1047,6 +1047,29 @@ static hipError_t run_batches(const DScene& sc, const DCamera& cam, const WaveAr
       gext[t] = cap(grid_for((const void*)k_extend<STACK, kCount, kVol, false, kQuant, kWide>, 256, 0, nslots, cus));
     }
     if (plan.bounces_run) *plan.bounces_run = 0;
+    if (plan.feat_acc) {
+      // feature mode: the camera rays' closest hits exactly as a render's
+      // bounce 0 finds them, then k_features in k_shade's place
+      for (int t = 0; t < nt; ++t) {
+        const WaveArgs& a = as[t];
+        const hipStream_t st = sts[t];
+        const uint32_t nslots = sb * a.npix;
+        if ((e = mark_begin(plan, uint8_t(KC_EXTEND | (t << KC_TWIN_SHIFT)), st)) != hipSuccess) return e;
+        hipLaunchKernelGGL((k_extend<STACK, kCount, kVol, true, kQuant, kWide>), dim3(gext0[t]), dim3(256), 0, st, sc, cam, a,
+                           a.s[0], a.counts + CNT_STREAM0, a.counts + CNT_STREAM1, a.counts + cnt_shadow(0),
+                           a.counts + cnt_fetch_sh(0), a.counts + CNT_FETCH_EXT, sample_base);
+        if ((e = mark_end(plan, st)) != hipSuccess) return e;
+        RTG_LAUNCHED("k_extend", 0, st);
+        if ((e = launch_features(sc, cam, a.hit, a.pixels, a.npix, nslots, a.seed, sample_base, a.s[0].o, a.s[0].d,
+                                 st)) != hipSuccess)
+          return e;
+        RTG_LAUNCHED("k_features", 0, st);
+        if ((e = launch_feat_accum(a.s[0].o, a.s[0].d, a.npix, sb, plan.feat_acc[t], cus, st)) != hipSuccess) return e;
+        RTG_LAUNCHED("k_feat_accum", 0, st);
+      }
+      if (plan.bounces_run) *plan.bounces_run = 1;
+      continue;
+    }
     // Bounce overlap (plan.overlap, scenes with lights): k_shadow and
     // k_nee_apply of bounce b run on the twin's aux stream while its k_extend
     // of bounce b + 1 (which needs only k_shade b's survivors) runs on its own
@@ -1235,8 +1258,13 @@ hipError_t launch_wavefront(const DScene& sc, const DCamera& cam, const WaveArgs
                             const WavePlan& plan, bool count, float* out, int accumulate) {
   hipError_t e;
   const int nt = plan.num_twins;
-  for (int t = 0; t < nt; ++t)
-    if ((e = hipMemsetAsync(as[t].acc, 0, size_t(as[t].npix) * 3 * sizeof(double), sts[t])) != hipSuccess) return e;
+  const bool feat = plan.feat_acc != nullptr;   // `out` is the feature image (features.h)
+  if (feat && (count || plan.max_depth != 1)) return hipErrorInvalidValue;
+  for (int t = 0; t < nt; ++t) {
+    if (feat) e = hipMemsetAsync(plan.feat_acc[t], 0, size_t(as[t].npix) * kFeatFloats * sizeof(double), sts[t]);
+    else e = hipMemsetAsync(as[t].acc, 0, size_t(as[t].npix) * 3 * sizeof(double), sts[t]);
+    if (e != hipSuccess) return e;
+  }
   if (plan.max_depth > 0) {
     // the kVol variants also carry the rare primitives (circles)
     // (and the reference-order closest hit of RotateX/Z scenes, DScene.dfs_order)
@@ -1253,6 +1281,13 @@ hipError_t launch_wavefront(const DScene& sc, const DCamera& cam, const WaveArgs
     else e = run_variant<8, false, false>(sc, cam, as, sts, plan);
 #endif
     if (e != hipSuccess) return e;
+  }
+  if (feat) {
+    for (int t = 0; t < nt; ++t)
+      if ((e = launch_feat_finalize(plan.feat_acc[t], as[t].pixels, as[t].npix, out, accumulate, plan.num_cus,
+                                    sts[t])) != hipSuccess)
+        return e;
+    return hipGetLastError();
   }
   if (!count)
     for (int t = 0; t < nt; ++t)

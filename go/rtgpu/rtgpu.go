@@ -546,8 +546,75 @@ func (c *Ctx) Tonemap(accum []float32, width, height, spp int, rgba []byte) erro
 		C.int32_t(height), C.int32_t(spp), (*C.uint8_t)(unsafe.Pointer(&rgba[0]))))
 }
 
+// RenderFeatures fills feat (Width*Height*8 float32: per pixel the sums over
+// the call's samples of albedo.rgb, normal.xyz, depth, coverage at the camera
+// rays' closest hits) for the same path keys as Render with the same Seed and
+// SampleOffset (rt_render_features); MaxDepth is ignored.  Blocks.
+func (c *Ctx) RenderFeatures(cam *CameraDesc, p RenderParams, feat []float32) (Stats, error) {
+	var st Stats
+	if len(feat) < int(cam.ImageWidth)*int(cam.ImageHeight)*8 {
+		return st, &Error{StatusInvalid, "feature buffer smaller than width*height*8"}
+	}
+	var pin runtime.Pinner
+	defer pin.Unpin()
+	prm := (*C.rt_render_params)(C.calloc(1, C.sizeof_rt_render_params))
+	defer C.free(unsafe.Pointer(prm))
+	prm.samples_per_pixel = C.int32_t(p.SamplesPerPixel)
+	prm.max_depth = C.int32_t(p.MaxDepth)
+	prm.sample_offset = C.int32_t(p.SampleOffset)
+	prm.seed = C.uint32_t(p.Seed)
+	if len(p.Buckets) > 0 {
+		pin.Pin(&p.Buckets[0])
+		prm.buckets = (*C.rt_bucket)(unsafe.Pointer(&p.Buckets[0]))
+		prm.num_buckets = C.int32_t(len(p.Buckets))
+	}
+	if p.Accumulate {
+		prm.accumulate = 1
+	}
+	rc := C.rt_render_features(c.p, (*C.rt_camera_desc)(unsafe.Pointer(cam)), prm,
+		(*C.float)(unsafe.Pointer(&feat[0])), (*C.rt_stats)(unsafe.Pointer(&st)))
+	return st, c.check(rc)
+}
+
+// DenoiseParams mirrors rt_denoise_params.
+//
+//rtgpu:mirror rt_denoise_params
+type DenoiseParams struct {
+	Iterations      int32   `c:"iterations"`
+	NormalPowerLog2 int32   `c:"normal_power_log2"`
+	Demodulate      int32   `c:"demodulate"`
+	SigmaColor      float32 `c:"sigma_color"`
+	SigmaDepth      float32 `c:"sigma_depth"`
+	AlbedoEps       float32 `c:"albedo_eps"`
+}
+
+// DefaultDenoiseParams returns rt_denoise_default_params.
+func DefaultDenoiseParams() DenoiseParams {
+	var p DenoiseParams
+	C.rt_denoise_default_params((*C.rt_denoise_params)(unsafe.Pointer(&p)))
+	return p
+}
+
+// Denoise filters accum (Width*Height*3 sums of spp samples) guided by feat
+// (RenderFeatures of the same samples) into out (rt_denoise); p nil = the
+// defaults.  For the preview passes: the final pass is shown as rendered.
+func (c *Ctx) Denoise(accum, feat []float32, width, height, spp int, p *DenoiseParams, out []float32) error {
+	if len(accum) < width*height*3 || len(feat) < width*height*8 || len(out) < width*height*3 {
+		return &Error{StatusInvalid, "denoise buffer too small"}
+	}
+	dp := DefaultDenoiseParams()
+	if p != nil {
+		dp = *p
+	}
+	return c.check(C.rt_denoise(c.p, (*C.float)(unsafe.Pointer(&accum[0])), (*C.float)(unsafe.Pointer(&feat[0])),
+		C.int32_t(width), C.int32_t(height), C.int32_t(spp), (*C.rt_denoise_params)(unsafe.Pointer(&dp)),
+		(*C.float)(unsafe.Pointer(&out[0]))))
+}
+
 // Layout checks: each mirror is exactly as large as its C struct.
 var (
+	_ [unsafe.Sizeof(DenoiseParams{}) - uintptr(C.sizeof_rt_denoise_params)]byte
+	_ [uintptr(C.sizeof_rt_denoise_params) - unsafe.Sizeof(DenoiseParams{})]byte
 	_ [unsafe.Sizeof(Node{}) - uintptr(C.sizeof_rt_hittable)]byte
 	_ [uintptr(C.sizeof_rt_hittable) - unsafe.Sizeof(Node{})]byte
 	_ [unsafe.Sizeof(Material{}) - uintptr(C.sizeof_rt_material)]byte

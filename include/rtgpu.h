@@ -497,6 +497,73 @@ int rt_extend_hits(rt_ctx* ctx, const rt_camera_desc* cam, uint32_t seed, int32_
 int rt_shadow_visibility(rt_ctx* ctx, const rt_camera_desc* cam, uint32_t seed, int32_t sample, int32_t bounce,
                          int32_t* out_nee);
 
+/* Feature buffers: per pixel 8 floats, albedo.rgb, normal.xyz, depth,
+ * coverage, each summed over the call's samples (the caller divides by the
+ * sample count, as for rt_render).  Sample s of a pixel uses the path key of
+ * rt_render's sample s (seed, sample_offset + s), so the features belong to
+ * the camera rays the frame traced; they are taken at that ray's closest hit
+ * as the integrator sees it (the production closest-hit kernel, lifted
+ * volumes included).  max_depth is ignored.  Per sample:
+ *   Lambertian / Isotropic: coverage 1, albedo = the texture's value at the
+ *     hit; Metal: its Albedo; Dielectric: (1,1,1);
+ *   normal = HitRecord.Normal (face-forwarded; (1,0,0) for a Volume,
+ *     volume.go:72-76), depth = the hit's ray parameter t (direction not
+ *     normalised).  Under a wrapper chain (Translate / Rotate / Scale) the
+ *     normal is the geometric one: the object-space HitRecord.Normal brought
+ *     to world space by each wrapper's true inverse and renormalised, so it
+ *     is unit and faces the ray.  (The integrator's own normal there is the
+ *     reference's as written: RotateX / RotateZ turn it by the ray's angle
+ *     again, transform.go:256-265, :337-346.)
+ *   miss or DiffuseLight: all eight floats 0 (noise-free at the camera ray;
+ *     rt_denoise passes such pixels through).
+ * buckets and accumulate as for rt_render: pixels outside the buckets are
+ * untouched, accumulate adds to the buffer's contents.  Sums are fp64 per
+ * pixel in sample order, rounded to float once per call: deterministic and
+ * independent of the schedule options.  rt_render_features blocks and takes
+ * a host buffer of width*height*8 floats; rt_render_features_device takes a
+ * device buffer and is asynchronous on `hip_stream` (device errors are
+ * reported as for rt_render_device).  A multi-device context runs the
+ * feature pass on its first device only, like the probes.
+ * rt_last_render_kernel_ms after either call reports the feature pass.      */
+int rt_render_features(rt_ctx* ctx, const rt_camera_desc* cam, const rt_render_params* params,
+                       float* feat, rt_stats* stats);
+int rt_render_features_device(rt_ctx* ctx, const rt_camera_desc* cam, const rt_render_params* params,
+                              float* feat_device, void* hip_stream);
+
+/* Edge-avoiding a-trous denoiser (Dammertz et al. 2010) guided by the feature
+ * buffers.  With the per-pixel means c = accum/spp and a, n, z, k = feat/spp
+ * (n not renormalised): a pixel with k < 0.5 is copied to the output bit for
+ * bit and is never a neighbour; the others filter e = c / max(a, albedo_eps)
+ * per channel (demodulate = 1; else e = c) by `iterations` passes, pass i with
+ * step 2^i over the 5x5 taps of the B3 spline [1/16, 1/4, 3/8, 1/4, 1/16]
+ * (taps outside the image skipped), each tap weighted by
+ *   max(0, n_p.n_q)^(2^normal_power_log2)
+ *   * exp(-|z_p - z_q| / (sigma_depth * |z_p| + 1e-6))
+ *   * exp(-|e_p - e_q|^2 / ((sigma_color * 2^-i)^2 + 1e-8)),
+ * and the result is e * max(a, albedo_eps) * spp (e * spp): sums again, so
+ * rt_tonemap_rgba8 takes it.  iterations = 0 copies the input.  Meant for the
+ * preview passes (1 spp, spp/4); it blurs what the features do not describe
+ * (reflections in Metal / Dielectric, shadows' edges): INTEGRATION.md.      */
+typedef struct rt_denoise_params {
+  int32_t iterations;        /* 0..8 a-trous passes, step 2^i; 0 copies the input      */
+  int32_t normal_power_log2; /* w_n = max(0, n_p.n_q)^(2^k), by k squarings (0..16)    */
+  int32_t demodulate;        /* 1: filter radiance / max(albedo, albedo_eps)           */
+  float sigma_color, sigma_depth, albedo_eps;
+} rt_denoise_params;
+/* iterations 5, normal_power_log2 5, demodulate 1, sigma_color 4, sigma_depth
+ * 0.1, albedo_eps 1e-3 (DESIGN.md "Feature buffers and denoiser").          */
+int rt_denoise_default_params(rt_denoise_params* out);
+/* Host arrays (accum_rgb, out_rgb: width*height*3; feat: width*height*8;
+ * `spp` = the samples both sums hold); blocks.  params NULL = the defaults.
+ * RT_ERR_INVALID: null pointers, non-positive sizes or spp, iterations
+ * outside 0..8, out_rgb overlapping accum_rgb.                             */
+int rt_denoise(rt_ctx* ctx, const float* accum_rgb, const float* feat, int32_t width, int32_t height,
+               int32_t spp, const rt_denoise_params* params, float* out_rgb);
+/* Same over device arrays (feat_dev 16-B aligned), asynchronous on
+ * `hip_stream`: one kernel launch per iteration.                           */
+int rt_denoise_device(rt_ctx* ctx, const float* accum_dev, const float* feat_dev, int32_t width, int32_t height,
+                      int32_t spp, const rt_denoise_params* params, float* out_dev, void* hip_stream);
+
 #ifdef __cplusplus
 }
 #endif
