@@ -22,6 +22,7 @@
 #include "flatten.h"
 #include "probe.h"
 #include "wavefront.h"
+#include "wave_layout.h"
 #include "denoise.h"
 
 using namespace rtg;
@@ -64,22 +65,16 @@ struct rt_ctx {
   std::vector<uint8_t> tev_class;
   int tev_used = 0;
   FlattenOptions fopt;
-  // schedule options (RT_OPT_BATCH_SLOTS / RT_OPT_REFILL / RT_OPT_MAX_BLOCKS;
-  // 0 = automatic): they change how the work is dealt, never the result
-  size_t opt_slots = 0;
-  int opt_refill = 0;
-  int opt_blocks = 0;
-  int opt_tail = 0;                     // RT_OPT_TAIL: 0 automatic, 1 off, > 1 the rays-left threshold
-  bool probing = false;                 // path_probe: every bounce through the wavefront kernels
-  // rt_render_features: the render path in its feature mode (WavePlan::feat_acc);
-  // wfacc = 8 fp64 sums per listed pixel, feat = the host variant's device image
-  bool feat_mode = false;
+  // schedule options (RT_OPT_BATCH_SLOTS / RT_OPT_REFILL / RT_OPT_MAX_BLOCKS /
+  // RT_OPT_TAIL / RT_OPT_STREAMS / RT_OPT_OVERLAP; 0 = automatic): they change
+  // how the work is dealt, never the result
+  WaveOptions wopt;
+  // rt_render_features (RenderRun::feat): wfacc = 8 fp64 sums per listed
+  // pixel, feat = the host variant's device image
   DevBuf wfacc, feat;
   // rt_denoise: the guide image and the two ping-pong images (one allocation),
   // and the host variant's device copies of its arrays
   DevBuf dn_work, dn_in, dn_feat, dn_out;
-  int opt_streams = 0;            // RT_OPT_STREAMS: 1..kMaxTwins twins (0 = automatic: kDefaultTwins)
-  int opt_overlap = 0;            // RT_OPT_OVERLAP: 0 automatic, 1 off, 2 on
   // bounce overlap (WavePlan::overlap): each twin's k_shadow / k_nee_apply
   // stream and the events that order it against the twin's own stream
   // (created at the first overlapped render)
@@ -306,279 +301,196 @@ int check_render_error(rt_ctx* ctx, bool wait) {
   return set_err(ctx, RT_ERR_DEVICE, "device traversal stack overflow in a render (its frame is wrong)");
 }
 
-// Twins per render unless RT_OPT_STREAMS / RTGPU_STREAMS say otherwise: three
-// for renders of more than kThreeTwinSamples samples (pixels x spp), two
-// below.  CornellBoxLucy full frame (405 M samples): one stream 1770, two
-// 1937-1952, three 1967-1970 Msamples/s; its 1/8 shards (51 M) are faster on
-// two (8-way shard prediction 6.94 / 6.99 vs 6.84 / 6.84 on three), its 1/2
-// shards (202 M) on three (2-way 1.908 / 1.917 vs 1.941 / 1.951), its 1/4
-// shards (101 M) alike (3.73 / 3.74 vs 3.75 / 3.75; round 4).
-constexpr int kDefaultTwins = 2;
-constexpr uint64_t kThreeTwinSamples = uint64_t(1) << 26;
-// With the bounce overlap each twin runs two streams: at most two twins, so
-// that the four streams keep a hardware queue each (GPU_MAX_HW_QUEUES = 4).
-constexpr int kOverlapTwins = 2;
+// How render_impl / render_wave run a render: where, what the caller wants
+// back, and which variant of the path.
+struct RenderRun {
+  hipStream_t st = nullptr;
+  double* ms = nullptr;                          // out: the render's span on `st` (the call then synchronises)
+  unsigned long long* host_counters = nullptr;   // out: CNT_WORDS work counters of an instrumented run (synchronises)
+  bool feat = false;      // rt_render_features: bounce 0's feature pass into the W*H*8 image `d_out` (WavePlan::feat_acc)
+  bool probing = false;   // path_probe: every bounce through the wavefront kernels
+};
 
-// Wavefront render (wavefront.hip): pixel list from the tiles, path-slot
-// batches sized to keep ~4M paths in flight.
-int render_wave(rt_ctx* ctx, const DCamera& dc, const rt_render_params* p, const std::vector<int4>& tiles, float* d_out,
-                hipStream_t st, bool count, unsigned long long* host_counters, double* ms) {
-  // Twins (wavefront.hip run_batches): tiles dealt alternately to two halves
-  // of the pixel list, each rendered on its own stream so one half's kernel
-  // tails overlap the other half's next kernel.  RT_OPT_STREAMS = 1 keeps one.
-  static const int env_twins = [] {
-    const char* e = getenv("RTGPU_STREAMS");
-    return e && atoi(e) > 0 ? std::min(kMaxTwins, atoi(e)) : 0;   // 0: automatic
-  }();
-  // Automatic = twins: CornellBoxLucy full frame 1770 (one stream) -> 1880
-  // Msamples/s, and the 1/8 shards gain more.
-  uint64_t tile_px = 0;
-  for (const int4& tl : tiles) tile_px += uint64_t(tl.z) * uint64_t(tl.w);
-  // Scenes whose shading runs the lifted volumes' tests (SHADE_VOL: C3's fog)
-  // render fastest on one stream: CornellBoxScene 600x600x1000 one / two /
-  // three parts 1605 / 1563 / 1557 Msamples/s (round 4).
-  const int auto_twins = ctx->dscene.shade_kind == SHADE_VOL ? 1
-                         : tile_px * uint64_t(std::max(1, p->samples_per_pixel)) > kThreeTwinSamples ? 3 : kDefaultTwins;
-  // Bounce overlap (run_batches) for scenes with lights: a second stream per
-  // twin.  RTGPU_OVERLAP (tuning knob) / RT_OPT_OVERLAP: 1 off, 2 on; off by
-  // default: measured slower on C4 at every twin count (DESIGN §3 "Bounce
-  // overlap": the full frame 2150 -> 2046 / 2025 Msamples/s on one / two
-  // twins, 8-way shard sums 218.8 -> 223.7 / 230.7 ms).
-  static const int env_overlap = [] {
-    const char* e = getenv("RTGPU_OVERLAP");
-    return e ? atoi(e) : 0;
-  }();
-  const int ovl_opt = ctx->opt_overlap ? ctx->opt_overlap : env_overlap;
-  const bool overlap = ctx->dscene.num_lights > 0 && ovl_opt == 2;
-  const int auto_twins2 = overlap ? std::min(auto_twins, kOverlapTwins) : auto_twins;
-  const int want_twins = ctx->opt_streams ? ctx->opt_streams : env_twins ? env_twins : auto_twins2;
-  const int nt = int(std::max<size_t>(1, std::min<size_t>(size_t(want_twins), tiles.size())));
-  std::vector<uint32_t>& px = ctx->pix_host;
-  px.clear();
-  uint32_t twin_npix[kMaxTwins] = {};
-  for (int t = 0; t < nt; ++t) {
-    const size_t before = px.size();
-    for (size_t k = size_t(t); k < tiles.size(); k += size_t(nt)) {
-      const int4& tl = tiles[k];
-      for (int y = tl.y; y < tl.y + tl.w; ++y)
-        for (int x = tl.x; x < tl.x + tl.z; ++x) px.push_back(uint32_t(y) * uint32_t(dc.width) + uint32_t(x));
-    }
-    twin_npix[t] = uint32_t(px.size() - before);
+// LDS stack ring (kLdsStack entries per lane) + global spill up to
+// kStackMax: scenes of any supported depth run with the small ring.
+#ifdef RTG_DIAG_RING
+constexpr int kRing = RTG_DIAG_RING;   // diagnostic builds (RTG_GUARD): the ring they were compiled for
+#else
+constexpr int kRing = kLdsStack;
+#endif
+
+// The pixel list to `wpix` through pinned staging (async-safe).
+int stage_pixels(rt_ctx* ctx, hipStream_t st) {
+  const size_t bytes = ctx->pix_host.size() * sizeof(uint32_t);
+  HIPCHK(hipEventSynchronize(ctx->pix_ev));   // the last render's copy has left the staging buffer
+  if (ctx->pix_pinned_n < ctx->pix_host.size()) {
+    if (ctx->pix_pinned) (void)hipHostFree(ctx->pix_pinned);
+    ctx->pix_pinned = nullptr;
+    ctx->pix_pinned_n = 0;
+    HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&ctx->pix_pinned), bytes));
+    ctx->pix_pinned_n = ctx->pix_host.size();
   }
-  const uint32_t npix = uint32_t(px.size());
-  const uint32_t spp = uint32_t(p->samples_per_pixel);
-  // Path slots per batch: as many as fit in 85 % of the free HBM, up to 2^30
-  // (249 GB at 232 B per slot).  Larger batches amortise every launch's
-  // ramp-down tail; measured on CornellBoxLucy (Msamples/s): 8M slots 501,
-  // 32M 686, 128M 759, 210M 799, the whole 405M-sample frame in one batch
-  // 833; on HDRITestScene 1920x1080 x 2000 spp, 8 batches of 518M slots 9571,
-  // 5 of 829M 9703, 4 of 1037M 9820 (profiles/r06_c5_slots_ab.log).  Samples
-  // are split evenly over the batches.  RTGPU_SLOTS overrides (tuning knob).
-  // When the automatic size does not fit after all (another process, or
-  // another context, took memory since hipMemGetInfo), it halves and retries.
-  // Per slot: kSlotF4 float4 arrays (wavefront.h) + job info + visibility
-  // words; kSlotF4Dark arrays and no job words in a scene without lights
-  // (C5: 128 instead of 232 B, three batches of 1.38G slots instead of four).
+  std::memcpy(ctx->pix_pinned, ctx->pix_host.data(), bytes);
+  HIPCHK(hipMemcpyAsync(ctx->wpix.p, ctx->pix_pinned, bytes, hipMemcpyHostToDevice, st));
+  HIPCHK(hipEventRecord(ctx->pix_ev, st));
+  return RT_OK;
+}
+
+// The bounce overlap's streams and events, created at the first overlapped render.
+int ensure_overlap_streams(rt_ctx* ctx) {
+  if (ctx->aux_st[0]) return RT_OK;
+  for (int t = 0; t < kMaxTwins; ++t) {
+    HIPCHK(hipStreamCreateWithFlags(&ctx->aux_st[t], hipStreamNonBlocking));
+    HIPCHK(hipEventCreateWithFlags(&ctx->ev_shade[t], hipEventDisableTiming));
+    HIPCHK(hipEventCreateWithFlags(&ctx->ev_nee[t], hipEventDisableTiming));
+  }
+  return RT_OK;
+}
+
+// Per-launch timing (rt_set_kernel_timing): at least `want` events for `plan`.
+int provision_timing(rt_ctx* ctx, WavePlan& plan, size_t want) {
+  while (ctx->tev.size() < want) {
+    hipEvent_t e = nullptr;
+    HIPCHK(hipEventCreate(&e));
+    ctx->tev.push_back(e);
+  }
+  ctx->tev_class.resize(ctx->tev.size());
+  plan.events = ctx->tev.data();
+  plan.ev_class = ctx->tev_class.data();
+  plan.max_events = int(ctx->tev.size());
+  plan.num_events = &ctx->tev_used;
+  return RT_OK;
+}
+
+#ifdef RTG_GUARD
+// Diagnostic build: reports the first out-of-range index of this render and
+// every scratch buffer whose canary was overwritten.
+int guard_render_report(rt_ctx* ctx, int nt) {
+  unsigned int gr[4] = {0, 0, 0, 0};
+  HIPCHK(guard_report(gr));
+  if (gr[0]) fprintf(stderr, "RTG_GUARD: %u bad indices, first at site %u: index %u >= length %u\n", gr[0], gr[1], gr[2], gr[3]);
+  const struct { const char* name; const DevBuf* b; } bufs[] = {
+      {"wstate", &ctx->wstate}, {"wq", &ctx->wq}, {"wpix", &ctx->wpix}, {"wacc", &ctx->wacc}, {"wfacc", &ctx->wfacc},
+      {"wspill", &ctx->wspill}, {"counters", &ctx->counters}, {"accum", &ctx->accum}, {"frame", &ctx->frame}};
+  for (const auto& x : bufs)
+    if (const size_t bad = canary_damage(*x.b))
+      fprintf(stderr, "RTG_GUARD: %zu canary bytes past %s (%zu bytes) overwritten (%d twins)\n", bad, x.name, x.b->bytes, nt);
+  return RT_OK;
+}
+#endif
+
+// Wavefront render (wavefront.hip) of the tiles' pixels.  wave_layout.h
+// decides the schedule and where every twin's arrays lie; this allocates,
+// binds and launches.
+int render_wave(rt_ctx* ctx, const DCamera& dc, const rt_render_params* p, const std::vector<int4>& tiles, float* d_out,
+                const RenderRun& run) {
+  hipStream_t st = run.st;
+  const bool count = run.host_counters != nullptr;
   const bool lit = ctx->dscene.num_lights > 0;
-  const size_t slot_f4 = size_t(lit ? kSlotF4 : kSlotF4Dark);
-  const size_t job_words = lit ? 2 : 0;
-  const size_t slot_bytes = slot_f4 * sizeof(float4) + job_words * sizeof(uint32_t);
-  constexpr size_t kMinSlots = size_t(1) << 20;
-  // at most 1.5 * 2^30 slots: a twin's slot indices stay below 2^31
-  constexpr size_t kMaxSlots = size_t(3) << 29;
-  static const size_t env_slots = [] {
-    const char* e = getenv("RTGPU_SLOTS");
-    return e && atol(e) > 0 ? size_t(atol(e)) : size_t(0);
-  }();
-  size_t target = ctx->opt_slots ? ctx->opt_slots : env_slots;
+  const uint32_t spp = uint32_t(p->samples_per_pixel);
+  int rc;
+  // the knobs, the twins, and the pixel list dealt to them
+  const WaveKnobs knobs = resolve_knobs(ctx->wopt, run.probing);
+  const bool overlap = use_overlap(knobs, lit);
+  const int nt = choose_twins(knobs, ctx->dscene.shade_kind == SHADE_VOL, overlap, tile_pixels(tiles),
+                              p->samples_per_pixel, tiles.size());
+  uint32_t twin_npix[kMaxTwins];
+  deal_pixels(tiles, dc.width, nt, ctx->pix_host, twin_npix);
+  const uint32_t npix = uint32_t(ctx->pix_host.size());
+  // path slots per batch, and the batch buffers: an automatic size that does
+  // not fit after all is halved and tried again
+  size_t target = knobs.slots;
   const bool auto_slots = target == 0;
   if (auto_slots) {
     size_t free_b = 0, total_b = 0;
     if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) free_b = size_t(8) << 30;
-    free_b += ctx->wstate.bytes + ctx->wq.bytes;   // the current batch buffers can be reused
-    target = std::min<size_t>(kMaxSlots, std::max<size_t>(kMinSlots, free_b / 100 * 85 / slot_bytes));
+    target = auto_target(free_b, ctx->wstate.bytes + ctx->wq.bytes, lit);
   }
-  uint32_t spb = 0;
-  size_t nslots = 0, wq_bytes = 0, f4_bytes = 0;
-  int rc;
+  BatchSize bs{};
   for (;;) {
-    const uint32_t max_spb = uint32_t(std::max<size_t>(1, std::min<size_t>(spp, target / npix)));
-    const uint32_t nbatch = (spp + max_spb - 1) / max_spb;
-    spb = (spp + nbatch - 1) / nbatch;
-    nslots = size_t(spb) * npix;   // over both twins
-    // Every twin takes slot_f4 float4 arrays of its S_t slots and, in `wq`,
-    // its CNT_WORDS_Q queue counters plus its job words: room for kMaxTwins
-    // twins' counters whatever `nt` this render uses (S_t sum to nslots over
-    // the twins).
-    f4_bytes = nslots * slot_f4 * sizeof(float4);
-    wq_bytes = (nslots * job_words + size_t(kMaxTwins) * CNT_WORDS_Q) * sizeof(uint32_t);
-    if (ctx->wstate.p && ctx->wq.p && ctx->wstate.bytes >= f4_bytes && ctx->wq.bytes >= wq_bytes) break;
+    bs = size_batch(spp, npix, target, lit);
+    if (ctx->wstate.p && ctx->wq.p && ctx->wstate.bytes >= bs.f4_bytes && ctx->wq.bytes >= bs.wq_bytes) break;
     free_buf(ctx->wstate);
     free_buf(ctx->wq);
-    rc = ensure(ctx, ctx->wstate, f4_bytes);
-    if (!rc) rc = ensure(ctx, ctx->wq, wq_bytes);
+    rc = ensure(ctx, ctx->wstate, bs.f4_bytes);
+    if (!rc) rc = ensure(ctx, ctx->wq, bs.wq_bytes);
     if (!rc) break;
-    if (rc != RT_ERR_OOM || !auto_slots || target <= kMinSlots || spb == 1) return rc;
+    if (rc != RT_ERR_OOM || !auto_slots || !can_halve(target, bs.spb)) return rc;
     free_buf(ctx->wstate);
     free_buf(ctx->wq);
     (void)hipGetLastError();
     ctx->error.clear();
-    target = std::max(kMinSlots, target / 2);
+    target = halve(target);
   }
+  // the other buffers
+  const SpillLayout spill = spill_layout(nt, overlap, ctx->num_cus, spill_cap_for(int(ctx->dscene.stack_needed), kRing));
   if ((rc = ensure(ctx, ctx->wpix, npix * sizeof(uint32_t)))) return rc;
   if ((rc = ensure(ctx, ctx->wacc, size_t(npix) * 3 * sizeof(double)))) return rc;
-  if (ctx->feat_mode && (rc = ensure(ctx, ctx->wfacc, size_t(npix) * kFeatFloats * sizeof(double)))) return rc;
+  if (run.feat && (rc = ensure(ctx, ctx->wfacc, size_t(npix) * kFeatFloats * sizeof(double)))) return rc;
   if ((rc = ensure(ctx, ctx->counters, CNT_WORDS * sizeof(unsigned long long)))) return rc;
-  // pixel list through pinned staging (async-safe)
-  HIPCHK(hipEventSynchronize(ctx->pix_ev));
-  if (ctx->pix_pinned_n < npix) {
-    if (ctx->pix_pinned) (void)hipHostFree(ctx->pix_pinned);
-    ctx->pix_pinned = nullptr;
-    ctx->pix_pinned_n = 0;
-    HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&ctx->pix_pinned), npix * sizeof(uint32_t)));
-    ctx->pix_pinned_n = npix;
-  }
-  std::memcpy(ctx->pix_pinned, px.data(), npix * sizeof(uint32_t));
-  HIPCHK(hipMemcpyAsync(ctx->wpix.p, ctx->pix_pinned, npix * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-  HIPCHK(hipEventRecord(ctx->pix_ev, st));
+  if ((rc = ensure(ctx, ctx->wspill, spill.words() * sizeof(uint32_t)))) return rc;
+  if ((rc = stage_pixels(ctx, st))) return rc;
   if (count) HIPCHK(hipMemsetAsync(ctx->counters.p, 0, CNT_WORDS * sizeof(unsigned long long), st));
-  // lanes that must want an item before a wave claims a new run (pool_take):
-  // within [1, 64] (the wave size), or no wave would ever claim
-  static const int refill = [] {
-    const char* e = getenv("RTGPU_REFILL");
-    return e ? std::min(64, std::max(1, atoi(e))) : 16;
-  }();
-  // LDS stack ring (kLdsStack entries per lane) + global spill up to
-  // kStackMax: scenes of any supported depth run with the small ring.
-#ifdef RTG_DIAG_RING
-  const int stack = RTG_DIAG_RING;   // diagnostic builds (RTG_GUARD): the ring they were compiled for
-#else
-  const int stack = kLdsStack;
-#endif
-  const uint32_t spill_lanes = uint32_t(std::max(1, ctx->num_cus)) * kSpillLanesPerCU;
-  // spill entries per lane: what the scene's stack bound leaves beyond the
-  // ring (flatten: stack_needed <= kStackMax; a deeper push is flagged)
-  const int spill_cap = std::max(1, std::min(kStackMax, int(ctx->dscene.stack_needed)) - stack);
-  const size_t spill_words = size_t(spill_lanes) * size_t(spill_cap);   // one spill area
-  // one area per twin, two with the bounce overlap (k_shadow beside k_extend)
-  const int spill_areas = nt * (overlap ? 2 : 1);
-  if ((rc = ensure(ctx, ctx->wspill, size_t(spill_areas) * spill_words * sizeof(uint32_t)))) return rc;
-  if (overlap && !ctx->aux_st[0])
-    for (int t = 0; t < kMaxTwins; ++t) {
-      HIPCHK(hipStreamCreateWithFlags(&ctx->aux_st[t], hipStreamNonBlocking));
-      HIPCHK(hipEventCreateWithFlags(&ctx->ev_shade[t], hipEventDisableTiming));
-      HIPCHK(hipEventCreateWithFlags(&ctx->ev_nee[t], hipEventDisableTiming));
-    }
-  // each twin: slot_f4 arrays of its own S_t slots, its queue counters and
-  // job words, its slice of the pixel list and the fp64 sums, its spill area
+  if (overlap && (rc = ensure_overlap_streams(ctx))) return rc;
+  // each twin's slices of those buffers, checked against what the buffers
+  // hold: nothing is launched otherwise
+  WaveCaps cap{};
+  cap.f4 = ctx->wstate.bytes / sizeof(float4);
+  cap.q = std::min(ctx->wq.bytes, bs.wq_bytes) / sizeof(uint32_t);
+  cap.pix = std::min(ctx->wpix.bytes / sizeof(uint32_t), ctx->wacc.bytes / (3 * sizeof(double)));
+  if (run.feat) cap.pix = std::min(cap.pix, ctx->wfacc.bytes / (kFeatFloats * sizeof(double)));
+  cap.spill = ctx->wspill.bytes / sizeof(uint32_t);
+  const WaveLayout lay = slice_twins(bs.spb, twin_npix, nt, lit, overlap, spill, cap);
+  if (!check(lay))
+    return set_err(ctx, RT_ERR_INVALID, "batch layout refused: a twin's slices leave the batch buffers or its slots reach 2^31");
   WaveArgs as[kMaxTwins]{};
   double* feat_acc[kMaxTwins] = {};   // feature mode: each twin's slice of wfacc
   hipStream_t sts[kMaxTwins] = {st};
   for (int t = 1; t < kMaxTwins; ++t) sts[t] = ctx->twin_st[t - 1];
-  float4* fbase = static_cast<float4*>(ctx->wstate.p);
-  uint32_t* qbase = static_cast<uint32_t*>(ctx->wq.p);
-  uint32_t pix_off = 0;
   for (int t = 0; t < nt; ++t) {
     WaveArgs& a = as[t];
-    const size_t S = size_t(spb) * twin_npix[t];
-    for (int k = 0; k < 2; ++k) {
-      float4* sb = fbase + size_t(3 * k) * S;
-      a.s[k] = PathStream{sb, sb + S, sb + 2 * S};
-    }
-    a.hit = fbase + 6 * S; a.Lout = fbase + 7 * S;
-    a.counts = qbase;
-    if (lit) {   // without lights no kernel touches the NEE job arrays
-      a.sj_p = fbase + 8 * S; a.sj_a = fbase + 9 * S; a.sj_h = fbase + 10 * S;
-      a.ne_a = fbase + 11 * S; a.ne_h = fbase + 12 * S; a.ne_beta = fbase + 13 * S;
-      a.sj_info = qbase + CNT_WORDS_Q;
-      a.sj_vis = a.sj_info + S;
-    }
-    fbase += slot_f4 * S;
-    qbase += CNT_WORDS_Q + job_words * S;
-    a.pixels = static_cast<const uint32_t*>(ctx->wpix.p) + pix_off;
-    a.npix = twin_npix[t];
-    a.acc = static_cast<double*>(ctx->wacc.p) + size_t(pix_off) * 3;
-    if (ctx->feat_mode) feat_acc[t] = static_cast<double*>(ctx->wfacc.p) + size_t(pix_off) * kFeatFloats;
-    pix_off += twin_npix[t];
+    bind_twin(a, static_cast<float4*>(ctx->wstate.p), static_cast<uint32_t*>(ctx->wq.p),
+              static_cast<const uint32_t*>(ctx->wpix.p), static_cast<double*>(ctx->wacc.p),
+              static_cast<uint32_t*>(ctx->wspill.p), lay.tw[t], lit);
+    if (run.feat) feat_acc[t] = static_cast<double*>(ctx->wfacc.p) + lay.tw[t].pix_off * kFeatFloats;
     a.seed = p->seed;
     a.max_depth = p->max_depth;
     a.counters = static_cast<unsigned long long*>(ctx->counters.p);
     a.err = static_cast<int*>(ctx->errflag.p);
-    a.refill = ctx->opt_refill ? ctx->opt_refill : refill;
-    a.spill_lanes = spill_lanes;
-    a.spill_cap = spill_cap;
-    a.spill = static_cast<uint32_t*>(ctx->wspill.p) + size_t(t) * spill_words;
-    a.spill_sh = overlap ? static_cast<uint32_t*>(ctx->wspill.p) + size_t(nt + t) * spill_words : a.spill;
-    a.slots = uint32_t(S);
+    a.refill = knobs.refill;
+    a.spill_lanes = spill.lanes;
+    a.spill_cap = spill.cap;
     a.out_pixels = uint32_t(dc.width) * uint32_t(dc.height);
     ctx->twin_args[t] = a;
   }
-  // the twins' slices must lie inside the batch buffers (an internal error
-  // otherwise: nothing is launched)
-  const size_t f4_used = size_t(fbase - static_cast<float4*>(ctx->wstate.p)) * sizeof(float4);
-  const size_t q_used = size_t(qbase - static_cast<uint32_t*>(ctx->wq.p)) * sizeof(uint32_t);
-  if (f4_used > ctx->wstate.bytes || q_used > ctx->wq.bytes || q_used > wq_bytes)
-    return set_err(ctx, RT_ERR_INVALID, "internal: twin buffers exceed the batch allocation");
   ctx->num_twins = nt;
   WavePlan plan{};
   plan.spp = spp;
-  plan.samples_per_batch = spb;
+  plan.samples_per_batch = bs.spb;
   plan.sample_offset = uint32_t(p->sample_offset);
   plan.max_depth = p->max_depth;
-  if (ctx->feat_mode) {   // bounce 0's closest hit only, whatever depth the caller's params name
+  if (run.feat) {   // bounce 0's closest hit only, whatever depth the caller's params name
     plan.max_depth = 1;
     plan.feat_acc = feat_acc;
   }
   plan.num_cus = ctx->num_cus;
-  // RTGPU_MAX_BLOCKS (tuning knob, like RTGPU_SLOTS): the option's default
-  static const int env_blocks = [] {
-    const char* e = getenv("RTGPU_MAX_BLOCKS");
-    return e && atoi(e) > 0 ? atoi(e) : 0;
-  }();
-  plan.max_blocks = ctx->opt_blocks ? ctx->opt_blocks : env_blocks;
+  plan.max_blocks = knobs.max_blocks;
   plan.num_twins = nt;
   plan.overlap = overlap ? 1 : 0;
   plan.aux = ctx->aux_st;
   plan.ev_shade = ctx->ev_shade;
   plan.ev_nee = ctx->ev_nee;
-  static const int debug_sync = [] {
-    const char* e = getenv("RTGPU_DEBUG_SYNC");
-    return e && atoi(e) > 0 ? 1 : 0;
-  }();
-  plan.debug_sync = debug_sync;
+  plan.debug_sync = knobs.debug_sync;
   plan.probe_host = ctx->probe_pinned;
   plan.bounces_run = &ctx->bounces_run;
-  // the long-tail kernel (k_tail): when at most this many paths are left in
-  // a deep render without lights; RTGPU_TAIL_RAYS sets the automatic value
-  static const int env_tail = [] {
-    const char* e = getenv("RTGPU_TAIL_RAYS");
-    return e ? atoi(e) : -1;
-  }();
-  const int auto_tail = env_tail >= 0 ? env_tail : kTailRaysDefault;
-  plan.tail_rays = ctx->probing || ctx->opt_tail == 1 ? 0u : uint32_t(ctx->opt_tail > 1 ? ctx->opt_tail : auto_tail);
-  static const int env_tail_first = [] {
-    const char* e = getenv("RTGPU_TAIL_FIRST");
-    return e ? atoi(e) : kTailFirstDefault;
-  }();
-  plan.tail_first = env_tail_first;
+  plan.tail_rays = knobs.tail_rays;
+  plan.tail_first = knobs.tail_first;
   ctx->tev_used = 0;
-  if (ctx->timing) {
-    // worst case: 2 events per timed launch, 3 timed launches per bounce, per batch and twin
-    const size_t batches = (spp + spb - 1) / spb;
-    const size_t want = std::min<size_t>(MAX_TIMING_EVENTS,
-                                         batches * size_t(std::max(1, p->max_depth)) * 6 * size_t(nt) + 4);
-    while (ctx->tev.size() < want) {
-      hipEvent_t e = nullptr;
-      HIPCHK(hipEventCreate(&e));
-      ctx->tev.push_back(e);
-    }
-    ctx->tev_class.resize(ctx->tev.size());
-    plan.events = ctx->tev.data();
-    plan.ev_class = ctx->tev_class.data();
-    plan.max_events = int(ctx->tev.size());
-    plan.num_events = &ctx->tev_used;
-  }
-  if (ms) HIPCHK(hipEventRecord(ctx->ev0, st));
+  if (ctx->timing &&
+      (rc = provision_timing(ctx, plan, timing_events_wanted(spp, bs.spb, p->max_depth, nt, MAX_TIMING_EVENTS))))
+    return rc;
+  // fan out to the twins' streams, launch, join
+  if (run.ms) HIPCHK(hipEventRecord(ctx->ev0, st));
   HIPCHK(hipEventRecord(ctx->kev0, st));
   if (nt > 1) {   // the other twins' streams start after the caller's stream reached here
     HIPCHK(hipEventRecord(ctx->twin_ev0, st));
@@ -591,41 +503,30 @@ int render_wave(rt_ctx* ctx, const DCamera& dc, const rt_render_params* p, const
   }
   HIPCHK(hipEventRecord(ctx->kev1, st));
   ctx->kev_recorded = true;
-  if (ms) HIPCHK(hipEventRecord(ctx->ev1, st));
+  if (run.ms) HIPCHK(hipEventRecord(ctx->ev1, st));
   // the render's error flag follows it to the host asynchronously; it is
   // read by the next entry point that synchronises (check_render_error)
   HIPCHK(hipMemcpyAsync(ctx->err_pinned, ctx->errflag.p, sizeof(int), hipMemcpyDeviceToHost, st));
   HIPCHK(hipEventRecord(ctx->err_ev, st));
   ctx->err_pending = true;
 #ifdef RTG_GUARD
-  {   // diagnostic build: report the first out-of-range index of this render
-    unsigned int gr[4] = {0, 0, 0, 0};
-    HIPCHK(guard_report(gr));
-    if (gr[0]) fprintf(stderr, "RTG_GUARD: %u bad indices, first at site %u: index %u >= length %u\n", gr[0], gr[1], gr[2], gr[3]);
-    const struct { const char* name; const DevBuf* b; } bufs[] = {
-        {"wstate", &ctx->wstate}, {"wq", &ctx->wq}, {"wpix", &ctx->wpix}, {"wacc", &ctx->wacc},
-        {"wspill", &ctx->wspill}, {"counters", &ctx->counters}, {"accum", &ctx->accum}, {"frame", &ctx->frame}};
-    for (const auto& x : bufs)
-      if (const size_t bad = canary_damage(*x.b))
-        fprintf(stderr, "RTG_GUARD: %zu canary bytes past %s (%zu bytes) overwritten (%d twins)\n", bad, x.name, x.b->bytes, nt);
-  }
+  if ((rc = guard_render_report(ctx, nt))) return rc;
 #endif
-  if (count || ms) {
+  if (count || run.ms) {
     if ((rc = check_render_error(ctx, true))) return rc;
-    if (ms) {
+    if (run.ms) {
       float f = 0.f;
       HIPCHK(hipEventElapsedTime(&f, ctx->ev0, ctx->ev1));
-      *ms = f;
+      *run.ms = f;
     }
     if (count)
-      HIPCHK(hipMemcpy(host_counters, ctx->counters.p, CNT_WORDS * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+      HIPCHK(hipMemcpy(run.host_counters, ctx->counters.p, CNT_WORDS * sizeof(unsigned long long), hipMemcpyDeviceToHost));
   }
   return RT_OK;
 }
 
 // Shared render path: tiles -> render kernel -> fixed-order reduce into `out`.
-int render_impl(rt_ctx* ctx, const rt_camera_desc* cam, const rt_render_params* p, float* d_out,
-                hipStream_t st, bool count, unsigned long long* host_counters, double* ms) {
+int render_impl(rt_ctx* ctx, const rt_camera_desc* cam, const rt_render_params* p, float* d_out, const RenderRun& run) {
   if (!ctx->has_scene) return set_err(ctx, RT_ERR_NO_SCENE, "no scene uploaded");
   if (!p) return set_err(ctx, RT_ERR_INVALID, "params is NULL");
   if (p->samples_per_pixel <= 0 || p->max_depth < 0 || p->sample_offset < 0)
@@ -637,7 +538,15 @@ int render_impl(rt_ctx* ctx, const rt_camera_desc* cam, const rt_render_params* 
   rc = make_tiles(ctx, p, dc.width, dc.height, tiles);
   if (rc) return rc;
   if (tiles.empty()) return RT_OK;
-  return render_wave(ctx, dc, p, tiles, d_out, st, count, host_counters, ms);
+  return render_wave(ctx, dc, p, tiles, d_out, run);
+}
+
+// Samples a render covers (rt_stats::samples): the buckets' pixels x spp.
+uint64_t covered_samples(const rt_camera_desc* cam, const rt_render_params* params) {
+  uint64_t px = 0;
+  if (params->buckets) for (int i = 0; i < params->num_buckets; ++i) px += uint64_t(params->buckets[i].width) * params->buckets[i].height;
+  else px = uint64_t(cam->image_width) * cam->image_height;
+  return px * uint64_t(params->samples_per_pixel);
 }
 
 // ---- multi-device contexts (rt_ctx_create_multi)
@@ -681,7 +590,7 @@ int render_share(rt_ctx* ctx, rt_ctx* primary, const rt_camera_desc* cam, const 
   const bool first = ctx == primary;
   hipStream_t s = first ? caller : ctx->stream;
   if (!first) HIPCHK(hipStreamWaitEvent(s, primary->fan_ev, 0));
-  int rc = render_impl(ctx, cam, &q, d_out, s, false, nullptr, nullptr);
+  int rc = render_impl(ctx, cam, &q, d_out, RenderRun{s});
   if (rc) return rc;
   if (!first) HIPCHK(hipEventRecord(ctx->join_ev, s));
   return RT_OK;
@@ -731,7 +640,7 @@ int render_dynamic(rt_ctx* ctx, const rt_camera_desc* cam, const rt_render_param
       rt_render_params q = *p;
       q.buckets = tiles.data() + cur;
       q.num_buckets = int32_t(run);
-      const int r = render_impl(c, cam, &q, d_out, s, false, nullptr, nullptr);
+      const int r = render_impl(c, cam, &q, d_out, RenderRun{s});
       if (r) return r;
       c->dealt_tiles += int32_t(run);
       c->dealt_runs += 1;
@@ -952,32 +861,32 @@ int rt_ctx_set_option(rt_ctx* ctx, int32_t key, int32_t value) {
   }
   if (key == RT_OPT_BATCH_SLOTS) {
     if (value < 0) return set_err(ctx, RT_ERR_INVALID, "bad batch slots");
-    ctx->opt_slots = size_t(value);
+    ctx->wopt.slots = size_t(value);
     return RT_OK;
   }
   if (key == RT_OPT_REFILL) {
     if (value < 0 || value > 64) return set_err(ctx, RT_ERR_INVALID, "refill must be 0 (default) or 1..64");
-    ctx->opt_refill = value;
+    ctx->wopt.refill = value;
     return RT_OK;
   }
   if (key == RT_OPT_STREAMS) {
     if (value < 0 || value > kMaxTwins) return set_err(ctx, RT_ERR_INVALID, "streams must be 0 (default) or 1..4");
-    ctx->opt_streams = value;
+    ctx->wopt.streams = value;
     return RT_OK;
   }
   if (key == RT_OPT_OVERLAP) {
     if (value < 0 || value > 2) return set_err(ctx, RT_ERR_INVALID, "overlap must be 0 (default), 1 (off) or 2 (on)");
-    ctx->opt_overlap = value;
+    ctx->wopt.overlap = value;
     return RT_OK;
   }
   if (key == RT_OPT_TAIL) {
     if (value < 0) return set_err(ctx, RT_ERR_INVALID, "bad tail option");
-    ctx->opt_tail = value;
+    ctx->wopt.tail = value;
     return RT_OK;
   }
   if (key == RT_OPT_MAX_BLOCKS) {
     if (value < 0) return set_err(ctx, RT_ERR_INVALID, "bad max blocks");
-    ctx->opt_blocks = value;
+    ctx->wopt.blocks = value;
     return RT_OK;
   }
   if (key == RT_OPT_DEALING) {
@@ -1239,7 +1148,7 @@ int rt_render(rt_ctx* ctx, const rt_camera_desc* cam, const rt_render_params* pa
   HIPCHK(hipMemcpyAsync(ctx->accum.p, accum_rgb, n * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
   double ms = 0.0;
   if (ctx->subs.empty()) {
-    rc = render_impl(ctx, cam, params, static_cast<float*>(ctx->accum.p), ctx->stream, false, nullptr, &ms);
+    rc = render_impl(ctx, cam, params, static_cast<float*>(ctx->accum.p), RenderRun{ctx->stream, &ms});
     if (rc) return rc;
   } else {
     // every device writes its buckets into this device's frame
@@ -1253,11 +1162,7 @@ int rt_render(rt_ctx* ctx, const rt_camera_desc* cam, const rt_render_params* pa
   HIPCHK(hipStreamSynchronize(ctx->stream));
   if (stats) {
     stats->kernel_ms = ms;
-    // pixels covered by the buckets x samples
-    uint64_t px = 0;
-    if (params->buckets) for (int i = 0; i < params->num_buckets; ++i) px += uint64_t(params->buckets[i].width) * params->buckets[i].height;
-    else px = uint64_t(cam->image_width) * cam->image_height;
-    stats->samples = px * uint64_t(params->samples_per_pixel);
+    stats->samples = covered_samples(cam, params);
   }
   return RT_OK;
 }
@@ -1271,7 +1176,7 @@ int rt_render_device(rt_ctx* ctx, const rt_camera_desc* cam, const rt_render_par
   // next rt_sync / rt_last_render_kernel_ms)
   int rc = check_render_error(ctx, false);
   if (rc) return rc;
-  if (ctx->subs.empty()) return render_impl(ctx, cam, params, accum_rgb_device, st, false, nullptr, nullptr);
+  if (ctx->subs.empty()) return render_impl(ctx, cam, params, accum_rgb_device, RenderRun{st});
   for (rt_ctx* s : ctx->subs) {
     HIPCHK(hipSetDevice(s->device));
     if ((rc = check_render_error(s, false))) return set_err(ctx, rc, s->error);
@@ -1294,18 +1199,14 @@ int rt_render_features(rt_ctx* ctx, const rt_camera_desc* cam, const rt_render_p
   if (rc) return rc;
   HIPCHK(hipMemcpyAsync(ctx->feat.p, feat, n * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
   double ms = 0.0;
-  ctx->feat_mode = true;
-  rc = render_impl(ctx, cam, params, static_cast<float*>(ctx->feat.p), ctx->stream, false, nullptr, &ms);
-  ctx->feat_mode = false;
-  if (rc) return rc;
+  RenderRun run{ctx->stream, &ms};
+  run.feat = true;
+  if ((rc = render_impl(ctx, cam, params, static_cast<float*>(ctx->feat.p), run))) return rc;
   HIPCHK(hipMemcpyAsync(feat, ctx->feat.p, n * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
   HIPCHK(hipStreamSynchronize(ctx->stream));
   if (stats) {
     stats->kernel_ms = ms;
-    uint64_t px = 0;
-    if (params->buckets) for (int i = 0; i < params->num_buckets; ++i) px += uint64_t(params->buckets[i].width) * params->buckets[i].height;
-    else px = uint64_t(cam->image_width) * cam->image_height;
-    stats->samples = px * uint64_t(params->samples_per_pixel);
+    stats->samples = covered_samples(cam, params);
   }
   return RT_OK;
 }
@@ -1317,10 +1218,9 @@ int rt_render_features_device(rt_ctx* ctx, const rt_camera_desc* cam, const rt_r
   hipStream_t st = hip_stream ? static_cast<hipStream_t>(hip_stream) : ctx->stream;
   int rc = check_render_error(ctx, false);
   if (rc) return rc;
-  ctx->feat_mode = true;
-  rc = render_impl(ctx, cam, params, feat_device, st, false, nullptr, nullptr);
-  ctx->feat_mode = false;
-  return rc;
+  RenderRun run{st};
+  run.feat = true;
+  return render_impl(ctx, cam, params, feat_device, run);
 }
 
 int rt_denoise_default_params(rt_denoise_params* p) {
@@ -1453,7 +1353,7 @@ int rt_count_work_by_kernel(rt_ctx* ctx, const rt_camera_desc* cam, const rt_ren
   HIPCHK(hipSetDevice(ctx->device));
   unsigned long long c[CNT_WORDS] = {0};
   double ms = 0.0;
-  int rc = render_impl(ctx, cam, params, nullptr, ctx->stream, true, c, &ms);
+  int rc = render_impl(ctx, cam, params, nullptr, RenderRun{ctx->stream, &ms, c});
   if (rc) return rc;
   for (int k = 0; k < 3; ++k) fill_counts(c + k * CNT_BLOCK, out + k);
   return RT_OK;
@@ -1592,7 +1492,7 @@ int rt_render_rgba8(rt_ctx* ctx, const rt_camera_desc* cam, const rt_render_para
       return set_err(ctx, RT_ERR_INVALID, "bucket outside the image");
   const auto t0 = std::chrono::steady_clock::now();
   float* fr = static_cast<float*>(ctx->frame.p);
-  if (ctx->subs.empty()) rc = render_impl(ctx, cam, params, fr, ctx->stream, false, nullptr, nullptr);
+  if (ctx->subs.empty()) rc = render_impl(ctx, cam, params, fr, RenderRun{ctx->stream});
   else rc = render_multi(ctx, cam, params, fr, ctx->stream);
   if (rc) return rc;
   if (!bk.empty()) {   // quantise the rendered buckets on the device (bucket_renderer.go:276-285)
@@ -1680,10 +1580,9 @@ int path_probe(rt_ctx* ctx, const rt_camera_desc* cam, uint32_t seed, int32_t sa
   const rt_render_params p{1, bounce + 1, sample, seed, nullptr, 0, 0};
   // the records of bounce k are read back from the wavefront kernels' arrays:
   // no long-tail kernel (it carries paths in registers)
-  ctx->probing = true;
-  rc = render_impl(ctx, cam, &p, static_cast<float*>(ctx->accum.p), ctx->stream, false, nullptr, nullptr);
-  ctx->probing = false;
-  if (rc) return rc;
+  RenderRun run{ctx->stream};
+  run.probing = true;
+  if ((rc = render_impl(ctx, cam, &p, static_cast<float*>(ctx->accum.p), run))) return rc;
   int32_t* top = static_cast<int32_t*>(ctx->probe.p);
   int32_t* prim = top + n;
   float* t = reinterpret_cast<float*>(prim + n);

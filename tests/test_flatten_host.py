@@ -9,7 +9,9 @@
   host, one lane per workgroup, driven batch by batch like run_batches()
   over exactly-sized buffers under AddressSanitizer + UBSan (every stream,
   job and queue index checked), with a 4-entry stack ring (spill path) and a
-  non-identity pixel list; compared with the oracle's fp32 mode.
+  non-identity pixel list; compared with the oracle's fp32 mode.  The arrays
+  per slot and the spill areas are sized as production sizes them
+  (wave_layout.h: no NEE job arrays without lights, spill_cap_for).
 """
 import json
 import os

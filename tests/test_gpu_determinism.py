@@ -121,6 +121,26 @@ def test_many_streams_fresh_context(g, streams):
     assert np.array_equal(frames[0], frames[1])
 
 
+def test_more_streams_than_tiles(g):
+    """Four twins asked for a render of one 16x16 tile: the twin count follows
+    the tiles (wave_layout.h choose_twins), and the frame equals the
+    one-stream frame bit for bit."""
+    s = g.Scene("cornell", width=32)
+    cam = s.camera
+    p = g.make_params(2, cam.max_depth, seed=SEED, buckets=[(0, 0, 16, 16)])
+    frames = []
+    for st in (4, 1):
+        c = g.Context(0)
+        try:
+            c.upload(s.desc)
+            c.set_option(g.RT_OPT_STREAMS, st)
+            frames.append(c.render(cam, p)[0])
+        finally:
+            c.close()
+    assert frames[0][:16, :16].sum() > 0 and frames[0][16:].sum() == 0
+    assert np.array_equal(frames[0], frames[1])
+
+
 def test_schedule_option_validation(g, ctx):
     with pytest.raises(g.RTError):
         ctx.set_option(g.RT_OPT_REFILL, 65)

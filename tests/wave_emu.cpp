@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "../go-raytracing_amd/csrc/wavefront.hip"
+#include "../go-raytracing_amd/csrc/wave_layout.h"
 #include "emu_scene.h"
 
 using namespace rtg;
@@ -93,12 +94,17 @@ int main(int argc, char** argv) {
   // exactly-sized buffers, one allocation per array (render_wave in api.cpp
   // carves the same arrays out of one buffer; separate ones let ASan see a
   // store that leaves its array)
-  std::vector<std::vector<float4>> f4(kSlotF4, std::vector<float4>(S, float4{0.0f, 0.0f, 0.0f, 0.0f}));
-  std::vector<uint32_t> q(CNT_WORDS_Q, 0u), sj_info(S, 0u), sj_vis(S, 0u);
+  // Sized as production sizes them (wave_layout.h): a scene without lights
+  // gets the first kSlotF4Dark arrays and no job words, and the spill areas
+  // hold what the scene's stack bound leaves beyond the ring.
+  const bool lit = d.num_lights > 0;
+  const int spill_cap = spill_cap_for(int(d.stack_needed), kRing);
+  std::vector<std::vector<float4>> f4(slot_f4(lit), std::vector<float4>(S, float4{0.0f, 0.0f, 0.0f, 0.0f}));
+  std::vector<uint32_t> q(CNT_WORDS_Q, 0u), sj_info(lit ? S : 0, 0u), sj_vis(lit ? S : 0, 0u);
   std::vector<uint32_t> pixels(npix);
   // bucket-like pixel list: reversed, so slot -> pixel is not the identity
   for (uint32_t i = 0; i < npix; ++i) pixels[i] = npix - 1u - i;
-  std::vector<uint32_t> spill(size_t(kStackMax - kRing), 0u), spill_sh(size_t(kStackMax - kRing), 0u);
+  std::vector<uint32_t> spill(size_t(spill_cap), 0u), spill_sh(size_t(spill_cap), 0u);
   std::vector<double> acc(size_t(npix) * 3, 0.0);
   std::vector<unsigned long long> counters(3 * CNT_BLOCK, 0ull);
   int err = 0;
@@ -107,11 +113,13 @@ int main(int argc, char** argv) {
   auto arr = [&](int k) { return f4[size_t(k)].data(); };
   for (int k = 0; k < 2; ++k) a.s[k] = PathStream{arr(3 * k), arr(3 * k + 1), arr(3 * k + 2)};
   a.hit = arr(6); a.Lout = arr(7);
-  a.sj_p = arr(8); a.sj_a = arr(9); a.sj_h = arr(10);
-  a.ne_a = arr(11); a.ne_h = arr(12); a.ne_beta = arr(13);
   a.counts = q.data();
-  a.sj_info = sj_info.data();
-  a.sj_vis = sj_vis.data();
+  if (lit) {   // as bind_twin: without lights the NEE job pointers stay null
+    a.sj_p = arr(8); a.sj_a = arr(9); a.sj_h = arr(10);
+    a.ne_a = arr(11); a.ne_h = arr(12); a.ne_beta = arr(13);
+    a.sj_info = sj_info.data();
+    a.sj_vis = sj_vis.data();
+  }
   a.pixels = pixels.data();
   a.npix = npix;
   a.acc = acc.data();
@@ -123,7 +131,7 @@ int main(int argc, char** argv) {
   a.spill = spill.data();
   a.spill_sh = spill_sh.data();
   a.spill_lanes = 1;
-  a.spill_cap = kStackMax - kRing;
+  a.spill_cap = spill_cap;
   a.slots = uint32_t(S);
   a.out_pixels = uint32_t(npix);
 

@@ -8,7 +8,6 @@ render; this script prints one line per render and the frame checksum.
 
   make -C go-raytracing_amd/csrc EXTRA="-DRTG_GUARD -DRTG_DIAG_RING=8" OUT=../lib_guard
   RTGPU_LIB_DIR=lib_guard python3 tools/guard_sweep.py
-  RTGPU_LIB_DIR=lib_guard RTGPU_GUARD_OLD_WQ=1 python3 tools/guard_sweep.py   # round-3 queue sizing
 """
 import os
 import sys
