@@ -123,6 +123,12 @@ class RtDenoiseParams(C.Structure):
                 ("sigma_color", C.c_float), ("sigma_depth", C.c_float), ("albedo_eps", C.c_float)]
 
 
+class RtDenoiseVarParams(C.Structure):
+    _fields_ = [("iterations", C.c_int32), ("normal_power_log2", C.c_int32), ("demodulate", C.c_int32),
+                ("spatial_below", C.c_int32), ("sigma_lum", C.c_float), ("sigma_depth", C.c_float),
+                ("albedo_eps", C.c_float)]
+
+
 class RtWorkCounts(C.Structure):
     _fields_ = [(n, C.c_uint64) for n in ("samples", "rays", "shadow_rays", "node_visits", "sphere_tests",
                                           "quad_tests", "tri_tests", "plane_tests", "instance_visits",
@@ -220,6 +226,16 @@ def rtgpu() -> C.CDLL:
             lib.rt_denoise.argtypes = [P, C.POINTER(C.c_float), C.POINTER(C.c_float), I32, I32, I32,
                                        C.POINTER(RtDenoiseParams), C.POINTER(C.c_float)]
             lib.rt_denoise_device.argtypes = [P, P, P, I32, I32, I32, C.POINTER(RtDenoiseParams), P, P]
+        if hasattr(lib, "rt_render_moments"):
+            lib.rt_render_moments.argtypes = [P, C.POINTER(RtCameraDesc), C.POINTER(RtRenderParams),
+                                              C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(RtStats)]
+            lib.rt_render_moments_device.argtypes = [P, C.POINTER(RtCameraDesc), C.POINTER(RtRenderParams), P, P, P]
+            lib.rt_denoise_variance_default_params.argtypes = [C.POINTER(RtDenoiseVarParams)]
+            lib.rt_denoise_variance.argtypes = [P, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float),
+                                                I32, I32, I32, C.POINTER(RtDenoiseVarParams), C.POINTER(C.c_float),
+                                                C.POINTER(C.c_float)]
+            lib.rt_denoise_variance_device.argtypes = [P, P, P, P, I32, I32, I32, C.POINTER(RtDenoiseVarParams), P, P,
+                                                       P]
         _rtgpu = lib
     return _rtgpu
 
@@ -419,6 +435,21 @@ def denoise_params(**overrides) -> RtDenoiseParams:
     return dp
 
 
+def denoise_variance_params(**overrides) -> RtDenoiseVarParams:
+    """rt_denoise_variance_default_params with keyword overrides (iterations,
+    normal_power_log2, demodulate, spatial_below, sigma_lum, sigma_depth,
+    albedo_eps)."""
+    dp = RtDenoiseVarParams()
+    rc = rtgpu().rt_denoise_variance_default_params(C.byref(dp))
+    if rc != RT_OK:
+        raise RTError(rc, "rt_denoise_variance_default_params failed")
+    for k, v in overrides.items():
+        if k not in dict(RtDenoiseVarParams._fields_):
+            raise TypeError(f"unknown denoise parameter {k!r}")
+        setattr(dp, k, v)
+    return dp
+
+
 # ---------------------------------------------------------------------------
 # GPU context (rt_ctx)
 # ---------------------------------------------------------------------------
@@ -548,6 +579,52 @@ class Context:
         dp = denoise_params(**params)
         self._check(self._lib.rt_denoise_device(self._h, C.c_void_p(accum_ptr), C.c_void_p(feat_ptr), width, height,
                                                 spp, C.byref(dp), C.c_void_p(out_ptr), C.c_void_p(stream)))
+
+    def render_moments(self, camera: RtCameraDesc, params: RtRenderParams, accum: Optional[np.ndarray] = None,
+                       moments: Optional[np.ndarray] = None):
+        """rt_render_moments: render()'s frame (the same bits) and the (H, W, 2)
+        float32 luminance moments (sum Y, sum Y^2) of the same samples; returns
+        (accum, moments, stats).  Both arrays accumulate with params.accumulate."""
+        if accum is None:
+            accum = np.zeros((camera.image_height, camera.image_width, 3), np.float32)
+        if moments is None:
+            moments = np.zeros((camera.image_height, camera.image_width, 2), np.float32)
+        st = RtStats()
+        self._check(self._lib.rt_render_moments(self._h, C.byref(camera), C.byref(params), _f32p(accum),
+                                                _f32p(moments), C.byref(st)))
+        return accum, moments, st
+
+    def render_moments_device(self, camera: RtCameraDesc, params: RtRenderParams, dev_ptr: int, moments_ptr: int,
+                              stream: int = 0):
+        self._check(self._lib.rt_render_moments_device(self._h, C.byref(camera), C.byref(params), C.c_void_p(dev_ptr),
+                                                       C.c_void_p(moments_ptr), C.c_void_p(stream)))
+
+    def denoise_variance(self, accum: np.ndarray, feat: np.ndarray, moments: Optional[np.ndarray], spp: int,
+                         return_variance: bool = False, **params):
+        """rt_denoise_variance: the variance-guided a-trous filter over (H, W, 3)
+        radiance sums, guided by the (H, W, 8) feature sums and the (H, W, 2)
+        moments of the same `spp` samples (moments may be None below
+        spatial_below samples); returns the filtered sums, with
+        return_variance also the (H, W) final variance.  Keyword arguments
+        override denoise_variance_params()'s defaults."""
+        h, w = accum.shape[:2]
+        out = np.zeros((h, w, 3), np.float32)
+        var = np.zeros((h, w), np.float32) if return_variance else None
+        dp = denoise_variance_params(**params)
+        self._check(self._lib.rt_denoise_variance(self._h, _f32p(accum), _f32p(feat),
+                                                  None if moments is None else _f32p(moments), w, h, spp,
+                                                  C.byref(dp), _f32p(out), None if var is None else _f32p(var)))
+        return (out, var) if return_variance else out
+
+    def denoise_variance_device(self, accum_ptr: int, feat_ptr: int, moments_ptr: int, width: int, height: int,
+                                spp: int, out_ptr: int, var_ptr: int = 0, stream: int = 0, **params):
+        """rt_denoise_variance_device: the same over device arrays (0 = NULL for
+        moments_ptr / var_ptr), asynchronous on `stream`."""
+        dp = denoise_variance_params(**params)
+        self._check(self._lib.rt_denoise_variance_device(self._h, C.c_void_p(accum_ptr), C.c_void_p(feat_ptr),
+                                                         C.c_void_p(moments_ptr or None), width, height, spp,
+                                                         C.byref(dp), C.c_void_p(out_ptr), C.c_void_p(var_ptr or None),
+                                                         C.c_void_p(stream)))
 
     def sync(self) -> None:
         """Wait for every enqueued render; raises RTError(RT_ERR_DEVICE) on a device error."""

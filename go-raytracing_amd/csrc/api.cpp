@@ -24,6 +24,7 @@
 #include "wavefront.h"
 #include "wave_layout.h"
 #include "denoise.h"
+#include "denoise_var.h"
 
 using namespace rtg;
 
@@ -75,6 +76,13 @@ struct rt_ctx {
   // rt_denoise: the guide image and the two ping-pong images (one allocation),
   // and the host variant's device copies of its arrays
   DevBuf dn_work, dn_in, dn_feat, dn_out;
+  // rt_render_moments (RenderRun::mom_out): wmacc = 2 fp64 sums per listed
+  // pixel, mom = the host variant's device image
+  DevBuf wmacc, mom;
+  // rt_denoise_variance: its working images (one allocation), and the host
+  // variant's device copies of the moments and the variance (the other
+  // arrays share rt_denoise's copies)
+  DevBuf dv_work, dv_mom, dv_var;
   // bounce overlap (WavePlan::overlap): each twin's k_shadow / k_nee_apply
   // stream and the events that order it against the twin's own stream
   // (created at the first overlapped render)
@@ -308,6 +316,7 @@ struct RenderRun {
   double* ms = nullptr;                          // out: the render's span on `st` (the call then synchronises)
   unsigned long long* host_counters = nullptr;   // out: CNT_WORDS work counters of an instrumented run (synchronises)
   bool feat = false;      // rt_render_features: bounce 0's feature pass into the W*H*8 image `d_out` (WavePlan::feat_acc)
+  float* mom_out = nullptr;   // rt_render_moments: also the W*H*2 moments image (WavePlan::mom_acc / mom_out)
   bool probing = false;   // path_probe: every bounce through the wavefront kernels
 };
 
@@ -371,6 +380,7 @@ int guard_render_report(rt_ctx* ctx, int nt) {
   if (gr[0]) fprintf(stderr, "RTG_GUARD: %u bad indices, first at site %u: index %u >= length %u\n", gr[0], gr[1], gr[2], gr[3]);
   const struct { const char* name; const DevBuf* b; } bufs[] = {
       {"wstate", &ctx->wstate}, {"wq", &ctx->wq}, {"wpix", &ctx->wpix}, {"wacc", &ctx->wacc}, {"wfacc", &ctx->wfacc},
+      {"wmacc", &ctx->wmacc},
       {"wspill", &ctx->wspill}, {"counters", &ctx->counters}, {"accum", &ctx->accum}, {"frame", &ctx->frame}};
   for (const auto& x : bufs)
     if (const size_t bad = canary_damage(*x.b))
@@ -427,6 +437,7 @@ int render_wave(rt_ctx* ctx, const DCamera& dc, const rt_render_params* p, const
   if ((rc = ensure(ctx, ctx->wpix, npix * sizeof(uint32_t)))) return rc;
   if ((rc = ensure(ctx, ctx->wacc, size_t(npix) * 3 * sizeof(double)))) return rc;
   if (run.feat && (rc = ensure(ctx, ctx->wfacc, size_t(npix) * kFeatFloats * sizeof(double)))) return rc;
+  if (run.mom_out && (rc = ensure(ctx, ctx->wmacc, size_t(npix) * kMomFloats * sizeof(double)))) return rc;
   if ((rc = ensure(ctx, ctx->counters, CNT_WORDS * sizeof(unsigned long long)))) return rc;
   if ((rc = ensure(ctx, ctx->wspill, spill.words() * sizeof(uint32_t)))) return rc;
   if ((rc = stage_pixels(ctx, st))) return rc;
@@ -439,12 +450,14 @@ int render_wave(rt_ctx* ctx, const DCamera& dc, const rt_render_params* p, const
   cap.q = std::min(ctx->wq.bytes, bs.wq_bytes) / sizeof(uint32_t);
   cap.pix = std::min(ctx->wpix.bytes / sizeof(uint32_t), ctx->wacc.bytes / (3 * sizeof(double)));
   if (run.feat) cap.pix = std::min(cap.pix, ctx->wfacc.bytes / (kFeatFloats * sizeof(double)));
+  if (run.mom_out) cap.pix = std::min(cap.pix, ctx->wmacc.bytes / (kMomFloats * sizeof(double)));
   cap.spill = ctx->wspill.bytes / sizeof(uint32_t);
   const WaveLayout lay = slice_twins(bs.spb, twin_npix, nt, lit, overlap, spill, cap);
   if (!check(lay))
     return set_err(ctx, RT_ERR_INVALID, "batch layout refused: a twin's slices leave the batch buffers or its slots reach 2^31");
   WaveArgs as[kMaxTwins]{};
   double* feat_acc[kMaxTwins] = {};   // feature mode: each twin's slice of wfacc
+  double* mom_acc[kMaxTwins] = {};    // moments mode: each twin's slice of wmacc
   hipStream_t sts[kMaxTwins] = {st};
   for (int t = 1; t < kMaxTwins; ++t) sts[t] = ctx->twin_st[t - 1];
   for (int t = 0; t < nt; ++t) {
@@ -453,6 +466,7 @@ int render_wave(rt_ctx* ctx, const DCamera& dc, const rt_render_params* p, const
               static_cast<const uint32_t*>(ctx->wpix.p), static_cast<double*>(ctx->wacc.p),
               static_cast<uint32_t*>(ctx->wspill.p), lay.tw[t], lit);
     if (run.feat) feat_acc[t] = static_cast<double*>(ctx->wfacc.p) + lay.tw[t].pix_off * kFeatFloats;
+    if (run.mom_out) mom_acc[t] = static_cast<double*>(ctx->wmacc.p) + lay.tw[t].pix_off * kMomFloats;
     a.seed = p->seed;
     a.max_depth = p->max_depth;
     a.counters = static_cast<unsigned long long*>(ctx->counters.p);
@@ -472,6 +486,10 @@ int render_wave(rt_ctx* ctx, const DCamera& dc, const rt_render_params* p, const
   if (run.feat) {   // bounce 0's closest hit only, whatever depth the caller's params name
     plan.max_depth = 1;
     plan.feat_acc = feat_acc;
+  }
+  if (run.mom_out) {
+    plan.mom_acc = mom_acc;
+    plan.mom_out = run.mom_out;
   }
   plan.num_cus = ctx->num_cus;
   plan.max_blocks = knobs.max_blocks;
@@ -798,6 +816,8 @@ void rt_ctx_destroy(rt_ctx* ctx) {
   free_buf(ctx->wspill);
   free_buf(ctx->wfacc); free_buf(ctx->feat);
   free_buf(ctx->dn_work); free_buf(ctx->dn_in); free_buf(ctx->dn_feat); free_buf(ctx->dn_out);
+  free_buf(ctx->wmacc); free_buf(ctx->mom);
+  free_buf(ctx->dv_work); free_buf(ctx->dv_mom); free_buf(ctx->dv_var);
   free_buf(ctx->frame); free_buf(ctx->frame_rgba); free_buf(ctx->frame_buckets);
   if (ctx->pix_pinned) (void)hipHostFree(ctx->pix_pinned);
   if (ctx->probe_pinned) (void)hipHostFree(ctx->probe_pinned);
@@ -1296,6 +1316,155 @@ int rt_denoise_device(rt_ctx* ctx, const float* accum_dev, const float* feat_dev
   HIPCHK(hipSetDevice(ctx->device));
   hipStream_t st = hip_stream ? static_cast<hipStream_t>(hip_stream) : ctx->stream;
   return denoise_impl(ctx, accum_dev, feat_dev, width, height, spp, params, out_dev, st);
+}
+
+// The render in its moments mode (moments.hip): the frame as rt_render
+// writes it, and the luminance moments of the same samples.
+static const char kMomentsMulti[] = "rt_render_moments on a multi-device context is not supported";
+
+int rt_render_moments(rt_ctx* ctx, const rt_camera_desc* cam, const rt_render_params* params, float* accum_rgb,
+                      float* moments, rt_stats* stats) {
+  if (!ctx || !cam || !params || !accum_rgb || !moments) return RT_ERR_INVALID;
+  HIPCHK(hipSetDevice(ctx->device));
+  if (!ctx->subs.empty()) return set_err(ctx, RT_ERR_UNSUPPORTED, kMomentsMulti);
+  if (cam->image_width <= 0 || cam->image_height <= 0) return set_err(ctx, RT_ERR_INVALID, "bad image size");
+  const size_t n = size_t(cam->image_width) * cam->image_height;
+  int rc;
+  if ((rc = ensure(ctx, ctx->accum, n * 3 * sizeof(float)))) return rc;
+  if ((rc = ensure(ctx, ctx->mom, n * kMomFloats * sizeof(float)))) return rc;
+  HIPCHK(hipMemcpyAsync(ctx->accum.p, accum_rgb, n * 3 * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(hipMemcpyAsync(ctx->mom.p, moments, n * kMomFloats * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+  double ms = 0.0;
+  RenderRun run{ctx->stream, &ms};
+  run.mom_out = static_cast<float*>(ctx->mom.p);
+  if ((rc = render_impl(ctx, cam, params, static_cast<float*>(ctx->accum.p), run))) return rc;
+  HIPCHK(hipMemcpyAsync(accum_rgb, ctx->accum.p, n * 3 * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(hipMemcpyAsync(moments, ctx->mom.p, n * kMomFloats * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  if (stats) {
+    stats->kernel_ms = ms;
+    stats->samples = covered_samples(cam, params);
+  }
+  return RT_OK;
+}
+
+int rt_render_moments_device(rt_ctx* ctx, const rt_camera_desc* cam, const rt_render_params* params,
+                             float* accum_rgb_device, float* moments_device, void* hip_stream) {
+  if (!ctx || !cam || !params || !accum_rgb_device || !moments_device) return RT_ERR_INVALID;
+  HIPCHK(hipSetDevice(ctx->device));
+  if (!ctx->subs.empty()) return set_err(ctx, RT_ERR_UNSUPPORTED, kMomentsMulti);
+  hipStream_t st = hip_stream ? static_cast<hipStream_t>(hip_stream) : ctx->stream;
+  int rc = check_render_error(ctx, false);
+  if (rc) return rc;
+  RenderRun run{st};
+  run.mom_out = moments_device;
+  return render_impl(ctx, cam, params, accum_rgb_device, run);
+}
+
+int rt_denoise_variance_default_params(rt_denoise_var_params* p) {
+  if (!p) return RT_ERR_INVALID;
+  p->iterations = 5;
+  p->normal_power_log2 = 5;
+  p->demodulate = 1;
+  p->spatial_below = 4;
+  p->sigma_lum = 8.0f;
+  p->sigma_depth = 0.1f;
+  p->albedo_eps = 1e-3f;
+  return RT_OK;
+}
+
+static bool ranges_overlap(const void* a, size_t na, const void* b, size_t nb) {
+  const char* a0 = static_cast<const char*>(a);
+  const char* b0 = static_cast<const char*>(b);
+  return a && b && a0 < b0 + nb && b0 < a0 + na;
+}
+
+// rt_denoise_variance / _device: the kernels of denoise_var.hip on `st` over
+// device arrays, with the context's working images.
+static int denoise_var_impl(rt_ctx* ctx, const float* accum, const float* feat, const float* moments, int32_t w,
+                            int32_t h, int32_t spp, const rt_denoise_var_params* params, float* out, float* out_var,
+                            hipStream_t st) {
+  rt_denoise_var_params dp;
+  rt_denoise_variance_default_params(&dp);
+  if (params) dp = *params;
+  if (w <= 0 || h <= 0 || spp <= 0) return set_err(ctx, RT_ERR_INVALID, "bad image size or samples");
+  if (dp.iterations < 0 || dp.iterations > kDvMaxIterations) return set_err(ctx, RT_ERR_INVALID, "iterations outside 0..8");
+  if (dp.normal_power_log2 < 0 || dp.normal_power_log2 > 16) return set_err(ctx, RT_ERR_INVALID, "normal_power_log2 outside 0..16");
+  if (!(dp.sigma_lum > 0.0f) || !(dp.sigma_depth >= 0.0f) || !(dp.albedo_eps > 0.0f))
+    return set_err(ctx, RT_ERR_INVALID, "sigma_lum / albedo_eps must be > 0, sigma_depth >= 0");
+  if (dp.spatial_below < 2) return set_err(ctx, RT_ERR_INVALID, "spatial_below must be >= 2");
+  const bool spatial = spp < dp.spatial_below;
+  if (!spatial && !moments) return set_err(ctx, RT_ERR_INVALID, "moments is NULL while spp >= spatial_below");
+  const size_t n = size_t(w) * size_t(h);
+  if (reinterpret_cast<uintptr_t>(feat) % 16 != 0) return set_err(ctx, RT_ERR_INVALID, "feature image not 16-B aligned");
+  // the passes read the inputs while the last one writes the outputs
+  if (ranges_overlap(accum, n * 12, out, n * 12)) return set_err(ctx, RT_ERR_INVALID, "output overlaps the input");
+  if (out_var && (ranges_overlap(out_var, n * 4, accum, n * 12) || ranges_overlap(out_var, n * 4, feat, n * 32) ||
+                  ranges_overlap(out_var, n * 4, moments, n * 8) || ranges_overlap(out_var, n * 4, out, n * 12)))
+    return set_err(ctx, RT_ERR_INVALID, "out_var overlaps an input or out_rgb");
+  if (dp.iterations == 0 && !out_var) {
+    HIPCHK(hipMemcpyAsync(out, accum, n * 3 * sizeof(float), hipMemcpyDeviceToDevice, st));
+    return RT_OK;
+  }
+  int rc = ensure(ctx, ctx->dv_work, n * kDvWorkBytesPerPixel);
+  if (rc) return rc;
+  DvArgs a{};
+  a.accum = accum; a.feat = feat; a.moments = spatial ? nullptr : moments; a.out = out; a.out_var = out_var;
+  a.guide = static_cast<float4*>(ctx->dv_work.p);
+  a.img[0] = a.guide + n; a.img[1] = a.guide + 2 * n;
+  a.var[0] = reinterpret_cast<float*>(a.guide + 3 * n); a.var[1] = a.var[0] + n;
+  a.w = w; a.h = h; a.spp = float(spp);
+  a.normal_power_log2 = dp.normal_power_log2; a.demodulate = dp.demodulate ? 1 : 0;
+  a.spatial = spatial ? 1 : 0;
+  a.sigma_lum = dp.sigma_lum; a.sigma_depth = dp.sigma_depth; a.albedo_eps = dp.albedo_eps;
+  HIPCHK(launch_denoise_var(a, dp.iterations, ctx->num_cus, st));
+  if (dp.iterations == 0) {   // the input, and the initial variance
+    HIPCHK(hipMemcpyAsync(out, accum, n * 3 * sizeof(float), hipMemcpyDeviceToDevice, st));
+    HIPCHK(hipMemcpyAsync(out_var, a.var[0], n * sizeof(float), hipMemcpyDeviceToDevice, st));
+  }
+  return RT_OK;
+}
+
+int rt_denoise_variance(rt_ctx* ctx, const float* accum_rgb, const float* feat, const float* moments, int32_t width,
+                        int32_t height, int32_t spp, const rt_denoise_var_params* params, float* out_rgb,
+                        float* out_var) {
+  if (!ctx || !accum_rgb || !feat || !out_rgb) return RT_ERR_INVALID;
+  HIPCHK(hipSetDevice(ctx->device));
+  if (width <= 0 || height <= 0 || spp <= 0) return set_err(ctx, RT_ERR_INVALID, "bad image size or samples");
+  const size_t n = size_t(width) * size_t(height);
+  // the host arrays' own overlaps (the device copies below never overlap)
+  if (ranges_overlap(accum_rgb, n * 12, out_rgb, n * 12)) return set_err(ctx, RT_ERR_INVALID, "output overlaps the input");
+  if (out_var && (ranges_overlap(out_var, n * 4, accum_rgb, n * 12) || ranges_overlap(out_var, n * 4, feat, n * 32) ||
+                  ranges_overlap(out_var, n * 4, moments, n * 8) || ranges_overlap(out_var, n * 4, out_rgb, n * 12)))
+    return set_err(ctx, RT_ERR_INVALID, "out_var overlaps an input or out_rgb");
+  int rc;
+  if ((rc = ensure(ctx, ctx->dn_in, n * 3 * sizeof(float)))) return rc;
+  if ((rc = ensure(ctx, ctx->dn_feat, n * kFeatFloats * sizeof(float)))) return rc;
+  if ((rc = ensure(ctx, ctx->dn_out, n * 3 * sizeof(float)))) return rc;
+  if (moments && (rc = ensure(ctx, ctx->dv_mom, n * kMomFloats * sizeof(float)))) return rc;
+  if (out_var && (rc = ensure(ctx, ctx->dv_var, n * sizeof(float)))) return rc;
+  HIPCHK(hipMemcpyAsync(ctx->dn_in.p, accum_rgb, n * 3 * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(hipMemcpyAsync(ctx->dn_feat.p, feat, n * kFeatFloats * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+  if (moments)
+    HIPCHK(hipMemcpyAsync(ctx->dv_mom.p, moments, n * kMomFloats * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+  if ((rc = denoise_var_impl(ctx, static_cast<const float*>(ctx->dn_in.p), static_cast<const float*>(ctx->dn_feat.p),
+                             moments ? static_cast<const float*>(ctx->dv_mom.p) : nullptr, width, height, spp, params,
+                             static_cast<float*>(ctx->dn_out.p), out_var ? static_cast<float*>(ctx->dv_var.p) : nullptr,
+                             ctx->stream)))
+    return rc;
+  HIPCHK(hipMemcpyAsync(out_rgb, ctx->dn_out.p, n * 3 * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+  if (out_var) HIPCHK(hipMemcpyAsync(out_var, ctx->dv_var.p, n * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  return RT_OK;
+}
+
+int rt_denoise_variance_device(rt_ctx* ctx, const float* accum_dev, const float* feat_dev, const float* moments_dev,
+                               int32_t width, int32_t height, int32_t spp, const rt_denoise_var_params* params,
+                               float* out_dev, float* out_var_dev, void* hip_stream) {
+  if (!ctx || !accum_dev || !feat_dev || !out_dev) return RT_ERR_INVALID;
+  HIPCHK(hipSetDevice(ctx->device));
+  hipStream_t st = hip_stream ? static_cast<hipStream_t>(hip_stream) : ctx->stream;
+  return denoise_var_impl(ctx, accum_dev, feat_dev, moments_dev, width, height, spp, params, out_dev, out_var_dev, st);
 }
 
 int rt_sync(rt_ctx* ctx) {

@@ -4,6 +4,7 @@
 #include <stdint.h>
 #include "dev_layout.h"
 #include "features.h"   // run_batches' feature mode launches features.hip's kernels
+#include "moments.h"    // ... and its moments mode moments.hip's
 
 namespace rtg {
 
@@ -118,6 +119,13 @@ struct WavePlan {
   // feature accumulate; feat_acc[t] holds twin t's 8 fp64 sums per listed
   // pixel, and launch_wavefront's `out` is the W*H*8 feature image.
   double* const* feat_acc;
+  // Moments mode (rt_render_moments, moments.hip): non-null = the render runs
+  // as ever and each batch's k_accum is followed by k_moment_accum over the
+  // same Lout entries, k_finalize by k_moment_finalize into `mom_out` (the
+  // W*H*2 moments image); mom_acc[t] holds twin t's 2 fp64 sums per listed
+  // pixel.  Not with feat_acc or an instrumented run.
+  double* const* mom_acc;
+  float* mom_out;
 };
 
 enum : uint8_t { KC_EXTEND = 0, KC_SHADE = 1, KC_SHADOW = 2, KC_OTHER = 3 };

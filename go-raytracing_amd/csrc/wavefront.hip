@@ -1187,6 +1187,10 @@ static hipError_t run_batches(const DScene& sc, const DCamera& cam, const WaveAr
         hipLaunchKernelGGL(k_accum, dim3(grid_for((const void*)k_accum, 256, 0, as[t].npix, cus)), dim3(256), 0, st,
                            as[t], sb);
         RTG_LAUNCHED("k_accum", plan.max_depth, st);
+        if (plan.mom_acc) {
+          if ((e = launch_moment_accum(as[t].Lout, as[t].npix, sb, plan.mom_acc[t], cus, st)) != hipSuccess) return e;
+          RTG_LAUNCHED("k_moment_accum", plan.max_depth, st);
+        }
       }
   }
   return hipGetLastError();
@@ -1260,10 +1264,15 @@ hipError_t launch_wavefront(const DScene& sc, const DCamera& cam, const WaveArgs
   const int nt = plan.num_twins;
   const bool feat = plan.feat_acc != nullptr;   // `out` is the feature image (features.h)
   if (feat && (count || plan.max_depth != 1)) return hipErrorInvalidValue;
+  const bool mom = plan.mom_acc != nullptr;     // the frame, and the moments image plan.mom_out (moments.h)
+  if (mom && (count || feat || !plan.mom_out)) return hipErrorInvalidValue;
   for (int t = 0; t < nt; ++t) {
     if (feat) e = hipMemsetAsync(plan.feat_acc[t], 0, size_t(as[t].npix) * kFeatFloats * sizeof(double), sts[t]);
     else e = hipMemsetAsync(as[t].acc, 0, size_t(as[t].npix) * 3 * sizeof(double), sts[t]);
     if (e != hipSuccess) return e;
+    if (mom && (e = hipMemsetAsync(plan.mom_acc[t], 0, size_t(as[t].npix) * kMomFloats * sizeof(double), sts[t])) !=
+                   hipSuccess)
+      return e;
   }
   if (plan.max_depth > 0) {
     // the kVol variants also carry the rare primitives (circles)
@@ -1293,6 +1302,11 @@ hipError_t launch_wavefront(const DScene& sc, const DCamera& cam, const WaveArgs
     for (int t = 0; t < nt; ++t)
       hipLaunchKernelGGL(k_finalize, dim3(grid_for((const void*)k_finalize, 256, 0, as[t].npix, plan.num_cus)),
                          dim3(256), 0, sts[t], as[t], out, accumulate);
+  if (mom)
+    for (int t = 0; t < nt; ++t)
+      if ((e = launch_moment_finalize(plan.mom_acc[t], as[t].pixels, as[t].npix, plan.mom_out, accumulate,
+                                      plan.num_cus, sts[t])) != hipSuccess)
+        return e;
   return hipGetLastError();
 }
 #endif  // RTG_WF_GROUP

@@ -611,8 +611,93 @@ func (c *Ctx) Denoise(accum, feat []float32, width, height, spp int, p *DenoiseP
 		(*C.float)(unsafe.Pointer(&out[0]))))
 }
 
+// RenderMoments renders as Render does (accum receives the same bits) and
+// also fills moments (Width*Height*2 float32: per pixel the sum and the sum
+// of squares of the samples' luminance), the guide of DenoiseVariance
+// (rt_render_moments).  Both buffers accumulate with p.Accumulate.  Blocks.
+func (c *Ctx) RenderMoments(cam *CameraDesc, p RenderParams, accum, moments []float32) (Stats, error) {
+	var st Stats
+	if len(accum) < int(cam.ImageWidth)*int(cam.ImageHeight)*3 {
+		return st, &Error{StatusInvalid, "accum buffer smaller than width*height*3"}
+	}
+	if len(moments) < int(cam.ImageWidth)*int(cam.ImageHeight)*2 {
+		return st, &Error{StatusInvalid, "moments buffer smaller than width*height*2"}
+	}
+	var pin runtime.Pinner
+	defer pin.Unpin()
+	prm := (*C.rt_render_params)(C.calloc(1, C.sizeof_rt_render_params))
+	defer C.free(unsafe.Pointer(prm))
+	prm.samples_per_pixel = C.int32_t(p.SamplesPerPixel)
+	prm.max_depth = C.int32_t(p.MaxDepth)
+	prm.sample_offset = C.int32_t(p.SampleOffset)
+	prm.seed = C.uint32_t(p.Seed)
+	if len(p.Buckets) > 0 {
+		pin.Pin(&p.Buckets[0])
+		prm.buckets = (*C.rt_bucket)(unsafe.Pointer(&p.Buckets[0]))
+		prm.num_buckets = C.int32_t(len(p.Buckets))
+	}
+	if p.Accumulate {
+		prm.accumulate = 1
+	}
+	rc := C.rt_render_moments(c.p, (*C.rt_camera_desc)(unsafe.Pointer(cam)), prm,
+		(*C.float)(unsafe.Pointer(&accum[0])), (*C.float)(unsafe.Pointer(&moments[0])),
+		(*C.rt_stats)(unsafe.Pointer(&st)))
+	return st, c.check(rc)
+}
+
+// DenoiseVarParams mirrors rt_denoise_var_params.
+//
+//rtgpu:mirror rt_denoise_var_params
+type DenoiseVarParams struct {
+	Iterations      int32   `c:"iterations"`
+	NormalPowerLog2 int32   `c:"normal_power_log2"`
+	Demodulate      int32   `c:"demodulate"`
+	SpatialBelow    int32   `c:"spatial_below"`
+	SigmaLum        float32 `c:"sigma_lum"`
+	SigmaDepth      float32 `c:"sigma_depth"`
+	AlbedoEps       float32 `c:"albedo_eps"`
+}
+
+// DefaultDenoiseVarParams returns rt_denoise_variance_default_params.
+func DefaultDenoiseVarParams() DenoiseVarParams {
+	var p DenoiseVarParams
+	C.rt_denoise_variance_default_params((*C.rt_denoise_var_params)(unsafe.Pointer(&p)))
+	return p
+}
+
+// DenoiseVariance filters accum (Width*Height*3 sums of spp samples) guided
+// by feat (RenderFeatures) and moments (RenderMoments) of the same samples
+// into out (rt_denoise_variance); p nil = the defaults.  moments may be nil
+// when spp is below SpatialBelow; outVar, if not nil, receives the filtered
+// variance (Width*Height).
+func (c *Ctx) DenoiseVariance(accum, feat, moments []float32, width, height, spp int, p *DenoiseVarParams,
+	out, outVar []float32) error {
+	if len(accum) < width*height*3 || len(feat) < width*height*8 || len(out) < width*height*3 {
+		return &Error{StatusInvalid, "denoise buffer too small"}
+	}
+	if (moments != nil && len(moments) < width*height*2) || (outVar != nil && len(outVar) < width*height) {
+		return &Error{StatusInvalid, "denoise buffer too small"}
+	}
+	dp := DefaultDenoiseVarParams()
+	if p != nil {
+		dp = *p
+	}
+	var mp, vp *C.float
+	if moments != nil {
+		mp = (*C.float)(unsafe.Pointer(&moments[0]))
+	}
+	if outVar != nil {
+		vp = (*C.float)(unsafe.Pointer(&outVar[0]))
+	}
+	return c.check(C.rt_denoise_variance(c.p, (*C.float)(unsafe.Pointer(&accum[0])),
+		(*C.float)(unsafe.Pointer(&feat[0])), mp, C.int32_t(width), C.int32_t(height), C.int32_t(spp),
+		(*C.rt_denoise_var_params)(unsafe.Pointer(&dp)), (*C.float)(unsafe.Pointer(&out[0])), vp))
+}
+
 // Layout checks: each mirror is exactly as large as its C struct.
 var (
+	_ [unsafe.Sizeof(DenoiseVarParams{}) - uintptr(C.sizeof_rt_denoise_var_params)]byte
+	_ [uintptr(C.sizeof_rt_denoise_var_params) - unsafe.Sizeof(DenoiseVarParams{})]byte
 	_ [unsafe.Sizeof(DenoiseParams{}) - uintptr(C.sizeof_rt_denoise_params)]byte
 	_ [uintptr(C.sizeof_rt_denoise_params) - unsafe.Sizeof(DenoiseParams{})]byte
 	_ [unsafe.Sizeof(Node{}) - uintptr(C.sizeof_rt_hittable)]byte

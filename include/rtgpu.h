@@ -564,6 +564,96 @@ int rt_denoise(rt_ctx* ctx, const float* accum_rgb, const float* feat, int32_t w
 int rt_denoise_device(rt_ctx* ctx, const float* accum_dev, const float* feat_dev, int32_t width, int32_t height,
                       int32_t spp, const rt_denoise_params* params, float* out_dev, void* hip_stream);
 
+/* Radiance moments: a render that also returns, per pixel, the first two
+ * moments of its samples' luminance.  `moments` holds width*height*2 floats,
+ * per pixel m1 = sum_s Y_s and m2 = sum_s Y_s^2 over the call's samples, with
+ *   Y = (0.2126 * L.x + 0.7152 * L.y) + 0.0722 * L.z
+ * of the sample's radiance L, the products and sums in fp64 as written (no
+ * fused multiply-add), the samples in the order the frame's own sums take
+ * them, each moment rounded to float once per call.  accum_rgb is what
+ * rt_render / rt_render_device writes for the same parameters, bit for bit:
+ * it is the same render with one small kernel more per batch.  buckets and
+ * accumulate as for rt_render, for both arrays: pixels outside the buckets are
+ * untouched, accumulate adds to the arrays' contents (so a progressive frame
+ * keeps the moments of all its samples).  Like the frame, the moments do not
+ * depend on the schedule options, the node format or the volume placement.
+ * From them the caller has the sample variance of a pixel's luminance,
+ * (m2 / n - (m1 / n)^2) * n / (n - 1), and rt_denoise_variance its guide.
+ * rt_render_moments blocks and takes host arrays; rt_render_moments_device
+ * takes device arrays and is asynchronous on `hip_stream` (device errors are
+ * reported as for rt_render_device).  rt_last_render_kernel_ms after either
+ * call covers the whole call.  RT_ERR_UNSUPPORTED on a multi-device context
+ * (rt_ctx_create_multi): render there with rt_render, or per device.        */
+int rt_render_moments(rt_ctx* ctx, const rt_camera_desc* cam, const rt_render_params* params,
+                      float* accum_rgb, float* moments, rt_stats* stats);
+int rt_render_moments_device(rt_ctx* ctx, const rt_camera_desc* cam, const rt_render_params* params,
+                             float* accum_rgb_device, float* moments_device, void* hip_stream);
+
+/* Variance-guided a-trous denoiser: the spatial part of SVGF (Schied et al.
+ * 2017).  rt_denoise with its colour weight replaced by a luminance weight
+ * that is scaled by the pixel's own standard deviation, and the variance
+ * filtered along with the colour.  All arithmetic is fp32 in a fixed order.
+ * As for rt_denoise: the means c = accum/spp and a, n, z, k = feat/spp; a
+ * pixel with k < 0.5 is copied to out_rgb bit for bit and is never a
+ * neighbour; e = c / max(a, albedo_eps) per channel (demodulate = 1; else
+ * e = c); the 5x5 B3 taps h, their order and the skipped taps; w_n, w_z; the
+ * result e * max(a, albedo_eps) * spp.  l(e) = (0.2126 e.x + 0.7152 e.y)
+ * + 0.0722 e.z.
+ * Initial variance v0(p), the variance of the pixel's mean expressed for l(e):
+ *   spp >= spatial_below: with n = spp, mu = m1 / n of `moments`
+ *     (rt_render_moments of the same samples),
+ *       var_Y = max(0, m2 / n - mu^2) / (n - 1)
+ *       v0 = var_Y / max(mu^2, 1e-12) * l(e_p)^2
+ *     i.e. the relative variance of Y carried over to l(e).  Demodulation
+ *     divides each channel by its own per-pixel constant: for a grey albedo
+ *     l(e) = Y / a and the transfer is exact, for a coloured one it is an
+ *     approximation.
+ *   spp < spatial_below (always at 1 spp; `moments` may be NULL): the weighted
+ *     variance of l(e_q) over the 7x7 unit-step window of covered pixels q,
+ *     weights w = w_n * w_z (1 for the centre), row-major:
+ *       v0 = max(0, sum w l^2 / sum w - (sum w l / sum w)^2)
+ * Pass i = 0 .. iterations - 1, step 2^i:
+ *   g(p) = the 3x3 Gaussian (1/4 centre, 1/8 edges, 1/16 corners) of the
+ *     current v at unit step over covered in-image neighbours, each weight
+ *     times w_n * w_z (1 for the centre), divided by the sum of the weights
+ *     used: like the taps, it does not reach across a geometric edge
+ *   w_l = exp(-|l(e_p) - l(e_q)| / (sigma_lum * sqrt(g(p)) + 1e-6))
+ *   w = w_n * w_z * w_l (1 for the centre tap)
+ *   e'(p) = sum h w e_q / sum h w
+ *   v'(p) = sum (h w)^2 v_q / (sum h w)^2
+ * sigma_lum is not halved per pass: the shrinking variance narrows the weight.
+ * A pixel whose samples disagree (a firefly) has a large v0, accepts its
+ * neighbours and is pulled to them, while a neighbour with a small variance
+ * still refuses it; rt_denoise, whose weight is centred on the pixel's own
+ * noisy value, leaves such a pixel as it is.  out_var, if not NULL, receives
+ * the final v (width*height floats; 0 for a passed-through pixel).
+ * iterations = 0 copies the input (out_var: v0).                            */
+typedef struct rt_denoise_var_params {
+  int32_t iterations;        /* 0..8 a-trous passes, step 2^i; 0 copies the input      */
+  int32_t normal_power_log2; /* as rt_denoise_params                                   */
+  int32_t demodulate;        /* as rt_denoise_params                                   */
+  int32_t spatial_below;     /* spp below this: the spatial variance estimate (>= 2)   */
+  float sigma_lum, sigma_depth, albedo_eps;
+} rt_denoise_var_params;
+/* iterations 5, normal_power_log2 5, demodulate 1, spatial_below 4, sigma_lum
+ * 8, sigma_depth 0.1, albedo_eps 1e-3 (DESIGN.md "Radiance moments and the
+ * variance-guided filter").                                                 */
+int rt_denoise_variance_default_params(rt_denoise_var_params* out);
+/* Host arrays (accum_rgb, out_rgb: width*height*3; feat: width*height*8;
+ * moments: width*height*2; out_var: width*height or NULL; `spp` = the samples
+ * the sums hold); blocks.  params NULL = the defaults.  RT_ERR_INVALID: what
+ * rt_denoise refuses, spatial_below < 2, moments NULL while spp >=
+ * spatial_below, out_var overlapping an input or out_rgb.                   */
+int rt_denoise_variance(rt_ctx* ctx, const float* accum_rgb, const float* feat, const float* moments,
+                        int32_t width, int32_t height, int32_t spp, const rt_denoise_var_params* params,
+                        float* out_rgb, float* out_var);
+/* Same over device arrays (feat_dev 16-B aligned), asynchronous on
+ * `hip_stream`: one launch for the initial variance (two in the spatial
+ * case) and one per iteration.                                              */
+int rt_denoise_variance_device(rt_ctx* ctx, const float* accum_dev, const float* feat_dev, const float* moments_dev,
+                               int32_t width, int32_t height, int32_t spp, const rt_denoise_var_params* params,
+                               float* out_dev, float* out_var_dev, void* hip_stream);
+
 #ifdef __cplusplus
 }
 #endif
