@@ -21,7 +21,9 @@
 // conservative and the closest hit (tie rule on the reference DFS ranks,
 // carried along in tri_rank) is the same for every builder.
 #include <hip/hip_runtime.h>
+#ifndef RTG_HOST_EMU   // tests/build_emu.cpp runs the kernels on the host and sorts with std::stable_sort
 #include <rocprim/device/device_radix_sort.hpp>
+#endif
 
 #include <vector>
 
@@ -215,6 +217,7 @@ __global__ __launch_bounds__(256) void k_tri_shade(const DTri* tris, const DTriA
   if (i < n) out[i] = make_tri_shade(tris[i], aux[i]);
 }
 
+#ifndef RTG_HOST_EMU
 // Device scratch of one build, freed on every exit path.
 struct Scratch {
   std::vector<void*> ptrs;
@@ -227,6 +230,7 @@ struct Scratch {
     for (void* p : ptrs) (void)hipFree(p);
   }
 };
+#endif
 
 #define BCHK(x)                          \
   do {                                   \
@@ -236,6 +240,7 @@ struct Scratch {
 
 inline unsigned blocks(uint32_t n) { return (n + 255u) / 256u; }
 
+#ifndef RTG_HOST_EMU
 template <class T>
 hipError_t gather(T* base, uint32_t n, const uint32_t* vals, Scratch& S, hipStream_t st) {
   T* tmp = nullptr;
@@ -244,14 +249,19 @@ hipError_t gather(T* base, uint32_t n, const uint32_t* vals, Scratch& S, hipStre
   BCHK(hipGetLastError());
   return hipMemcpyAsync(base, tmp, size_t(n) * sizeof(T), hipMemcpyDeviceToDevice, st);
 }
+#endif
 
 }  // namespace
 
+#ifndef RTG_HOST_EMU
 hipError_t build_mesh_blas(const DeviceBuildJob& job, const DRefBox* boxes, DeviceBuildTarget& tgt,
                            DeviceBuildResult& res, hipStream_t st) {
   const uint32_t n = job.n;
   res = DeviceBuildResult{};
   if (tgt.leaves_used + n > tgt.leaves_cap || tgt.nodes_used + n > tgt.nodes_cap) return hipErrorInvalidValue;
+  // Not reachable through the API: flatten queues a device build only for
+  // meshes of at least sah_min_prims (16) triangles.  Kept so the function
+  // is total over its arguments.
   if (n <= kMaxLeaf) {   // one leaf, triangles stay in DFS order
     const DLeaf lf{job.tri_first, make_leaf_info(int(n), PK_TRI, 1)};
     BCHK(hipMemcpyAsync(tgt.leaves + tgt.leaves_used, &lf, sizeof lf, hipMemcpyHostToDevice, st));
@@ -349,5 +359,6 @@ hipError_t pack_tri_shade(const DTri* tris, const DTriAux* aux, DTriShade* out, 
   BCHK(hipGetLastError());
   return hipStreamSynchronize(st);
 }
+#endif   // RTG_HOST_EMU
 
 }  // namespace rtg

@@ -22,6 +22,7 @@ struct uint4 { uint32_t x, y, z, w; };
 struct uint2 { uint32_t x, y; };
 struct int4 { int x, y, z, w; };
 inline float4 make_float4(float x, float y, float z, float w) { return float4{x, y, z, w}; }
+inline uint2 make_uint2(uint32_t x, uint32_t y) { return uint2{x, y}; }
 // Wave vote with random wave-mates: returns p, or true at random when p is
 // false (other lanes of the emulated wave still voting yes), so the
 // single-lane emulation also walks the "keep traversing while holding a
@@ -48,6 +49,8 @@ inline uint32_t __builtin_amdgcn_readfirstlane(uint32_t v) { return v; }
 inline int __popcll(unsigned long long x) { return __builtin_popcountll(x); }
 inline int __ffsll(unsigned long long x) { return __builtin_ffsll(static_cast<long long>(x)); }
 inline uint32_t atomicAdd(uint32_t* p, uint32_t v) { const uint32_t o = *p; *p = o + v; return o; }
+inline int atomicMax(int* p, int v) { const int o = *p; if (v > o) *p = v; return o; }
+inline void __threadfence() {}   // lanes run one after another: every store is already visible
 inline void atomicAddNoRet(float* p, float v) { *p = *p + v; }   // one lane: the plain add
 inline unsigned long long atomicAdd(unsigned long long* p, unsigned long long v) {
   const unsigned long long o = *p; *p = o + v; return o;

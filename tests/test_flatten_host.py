@@ -12,6 +12,11 @@
   non-identity pixel list; compared with the oracle's fp32 mode.  The arrays
   per slot and the spill areas are sized as production sizes them
   (wave_layout.h: no NEE job arrays without lights, spill_cap_for).
+
+The other kernel files have host emulations of their own, built the same way:
+tests/denoise_emu.cpp (test_denoise_host.py), tests/denoise_var_emu.cpp
+(test_denoise_var_host.py) and tests/build_emu.cpp, the device BVH build's
+kernels of build.hip (test_device_build_host.py).
 """
 import json
 import os
