@@ -129,6 +129,16 @@ class RtDenoiseVarParams(C.Structure):
                 ("albedo_eps", C.c_float)]
 
 
+class RtAdaptiveParams(C.Structure):
+    _fields_ = [("min_spp", C.c_int32), ("step_spp", C.c_int32), ("neighbourhood", C.c_int32),
+                ("rel_error", C.c_float), ("lum_floor", C.c_float)]
+
+
+class RtAdaptiveStats(C.Structure):
+    _fields_ = [("kernel_ms", C.c_double), ("samples", C.c_uint64), ("rounds", C.c_int32),
+                ("pixels_at_max", C.c_int32)]
+
+
 class RtWorkCounts(C.Structure):
     _fields_ = [(n, C.c_uint64) for n in ("samples", "rays", "shadow_rays", "node_visits", "sphere_tests",
                                           "quad_tests", "tri_tests", "plane_tests", "instance_visits",
@@ -236,6 +246,20 @@ def rtgpu() -> C.CDLL:
                                                 C.POINTER(C.c_float)]
             lib.rt_denoise_variance_device.argtypes = [P, P, P, P, I32, I32, I32, C.POINTER(RtDenoiseVarParams), P, P,
                                                        P]
+        if hasattr(lib, "rt_render_adaptive"):
+            U32P = C.POINTER(U32)
+            lib.rt_adaptive_default_params.argtypes = [C.POINTER(RtAdaptiveParams)]
+            lib.rt_render_adaptive.argtypes = [P, C.POINTER(RtCameraDesc), C.POINTER(RtRenderParams),
+                                               C.POINTER(RtAdaptiveParams), C.POINTER(C.c_float),
+                                               C.POINTER(C.c_float), U32P, C.POINTER(RtAdaptiveStats)]
+            lib.rt_render_adaptive_device.argtypes = [P, C.POINTER(RtCameraDesc), C.POINTER(RtRenderParams),
+                                                      C.POINTER(RtAdaptiveParams), P, P, P,
+                                                      C.POINTER(RtAdaptiveStats), P]
+            lib.rt_adaptive_select.argtypes = [P, C.POINTER(C.c_float), U32P, I32, I32, I32,
+                                               C.POINTER(RtAdaptiveParams), U32P, U32P]
+            lib.rt_normalize_samples.argtypes = [P, C.POINTER(C.c_float), I32, U32P, I32, I32, I32,
+                                                 C.POINTER(C.c_float)]
+            lib.rt_normalize_samples_device.argtypes = [P, P, I32, P, I32, I32, I32, P, P]
         _rtgpu = lib
     return _rtgpu
 
@@ -293,6 +317,12 @@ def _f32p(a: np.ndarray):
 
 def _i32p(a: np.ndarray):
     return a.ctypes.data_as(C.POINTER(C.c_int32))
+
+
+def _u32p(a: np.ndarray):
+    if a.dtype != np.uint32 or not a.flags["C_CONTIGUOUS"]:
+        raise TypeError("a contiguous uint32 array is needed")
+    return a.ctypes.data_as(C.POINTER(C.c_uint32))
 
 
 # ---------------------------------------------------------------------------
@@ -448,6 +478,20 @@ def denoise_variance_params(**overrides) -> RtDenoiseVarParams:
             raise TypeError(f"unknown denoise parameter {k!r}")
         setattr(dp, k, v)
     return dp
+
+
+def adaptive_params(**overrides) -> RtAdaptiveParams:
+    """rt_adaptive_default_params with keyword overrides (min_spp, step_spp,
+    neighbourhood, rel_error, lum_floor)."""
+    ap = RtAdaptiveParams()
+    rc = rtgpu().rt_adaptive_default_params(C.byref(ap))
+    if rc != RT_OK:
+        raise RTError(rc, "rt_adaptive_default_params failed")
+    for k, v in overrides.items():
+        if k not in dict(RtAdaptiveParams._fields_):
+            raise TypeError(f"unknown adaptive parameter {k!r}")
+        setattr(ap, k, v)
+    return ap
 
 
 # ---------------------------------------------------------------------------
@@ -625,6 +669,70 @@ class Context:
                                                          C.c_void_p(moments_ptr or None), width, height, spp,
                                                          C.byref(dp), C.c_void_p(out_ptr), C.c_void_p(var_ptr or None),
                                                          C.c_void_p(stream)))
+
+    def render_adaptive(self, camera: RtCameraDesc, params: RtRenderParams, accum: Optional[np.ndarray] = None,
+                        moments: Optional[np.ndarray] = None, counts: Optional[np.ndarray] = None, **adaptive):
+        """rt_render_adaptive: params.samples_per_pixel is the budget max_spp; a
+        pixel stops being sampled once its luminance's standard error is small
+        enough.  Returns (accum, moments, counts, stats): the (H, W, 3) sums and
+        (H, W, 2) moments of each pixel's first counts[p] samples and the
+        (H, W) uint32 counts.  Keyword arguments override adaptive_params()'s
+        defaults.  Blocks."""
+        h, w = camera.image_height, camera.image_width
+        if accum is None:
+            accum = np.zeros((h, w, 3), np.float32)
+        if moments is None:
+            moments = np.zeros((h, w, 2), np.float32)
+        if counts is None:
+            counts = np.zeros((h, w), np.uint32)
+        ap = adaptive_params(**adaptive)
+        st = RtAdaptiveStats()
+        self._check(self._lib.rt_render_adaptive(self._h, C.byref(camera), C.byref(params), C.byref(ap),
+                                                 _f32p(accum), _f32p(moments), _u32p(counts), C.byref(st)))
+        return accum, moments, counts, st
+
+    def render_adaptive_device(self, camera: RtCameraDesc, params: RtRenderParams, dev_ptr: int, moments_ptr: int,
+                               counts_ptr: int, stream: int = 0, **adaptive) -> RtAdaptiveStats:
+        """rt_render_adaptive_device: the same into device arrays (counts: 4-byte
+        unsigned words); blocks, like the host variant."""
+        ap = adaptive_params(**adaptive)
+        st = RtAdaptiveStats()
+        self._check(self._lib.rt_render_adaptive_device(self._h, C.byref(camera), C.byref(params), C.byref(ap),
+                                                        C.c_void_p(dev_ptr), C.c_void_p(moments_ptr),
+                                                        C.c_void_p(counts_ptr), C.byref(st), C.c_void_p(stream)))
+        return st
+
+    def adaptive_select(self, moments: np.ndarray, counts: np.ndarray, max_spp: int, **adaptive) -> np.ndarray:
+        """rt_adaptive_select: the ascending ids of the pixels of (H, W, 2)
+        moments / (H, W) uint32 counts that stay active (counts 0: not in the
+        call, >= max_spp: done)."""
+        h, w = counts.shape
+        ap = adaptive_params(**adaptive)
+        out = np.zeros(h * w, np.uint32)
+        n = C.c_uint32(0)
+        self._check(self._lib.rt_adaptive_select(self._h, _f32p(moments), _u32p(counts), w, h, max_spp, C.byref(ap),
+                                                 _u32p(out), C.byref(n)))
+        return out[:n.value].copy()
+
+    def normalize_samples(self, sums: np.ndarray, counts: np.ndarray, target_spp: int,
+                          out: Optional[np.ndarray] = None) -> np.ndarray:
+        """rt_normalize_samples: (H, W, C) sums over counts[p] samples each to
+        sums over target_spp samples, (sums / counts) * target_spp; `out` may
+        be `sums`."""
+        h, w = counts.shape
+        channels = sums.size // (h * w)
+        if out is None:
+            out = np.zeros(sums.shape, np.float32)
+        self._check(self._lib.rt_normalize_samples(self._h, _f32p(sums), channels, _u32p(counts), w, h, target_spp,
+                                                   _f32p(out)))
+        return out
+
+    def normalize_samples_device(self, sums_ptr: int, channels: int, counts_ptr: int, width: int, height: int,
+                                 target_spp: int, out_ptr: int, stream: int = 0):
+        """rt_normalize_samples_device: the same over device arrays, asynchronous on `stream`."""
+        self._check(self._lib.rt_normalize_samples_device(self._h, C.c_void_p(sums_ptr), channels,
+                                                          C.c_void_p(counts_ptr), width, height, target_spp,
+                                                          C.c_void_p(out_ptr), C.c_void_p(stream)))
 
     def sync(self) -> None:
         """Wait for every enqueued render; raises RTError(RT_ERR_DEVICE) on a device error."""

@@ -25,6 +25,7 @@
 #include "wave_layout.h"
 #include "denoise.h"
 #include "denoise_var.h"
+#include "adaptive.h"
 
 using namespace rtg;
 
@@ -83,6 +84,13 @@ struct rt_ctx {
   // variant's device copies of the moments and the variance (the other
   // arrays share rt_denoise's copies)
   DevBuf dv_work, dv_mom, dv_var;
+  // rt_render_adaptive: ad_work = the working count image, the call's pixel
+  // list, the selection's flags and block counts (one allocation; the active
+  // list itself is written into wpix, where render_wave reads it), ad_counts =
+  // the host variants' device copy of the caller's count image, ad_pinned =
+  // where a round's list length reaches the host
+  DevBuf ad_work, ad_counts;
+  uint32_t* ad_pinned = nullptr;
   // bounce overlap (WavePlan::overlap): each twin's k_shadow / k_nee_apply
   // stream and the events that order it against the twin's own stream
   // (created at the first overlapped render)
@@ -318,6 +326,11 @@ struct RenderRun {
   bool feat = false;      // rt_render_features: bounce 0's feature pass into the W*H*8 image `d_out` (WavePlan::feat_acc)
   float* mom_out = nullptr;   // rt_render_moments: also the W*H*2 moments image (WavePlan::mom_acc / mom_out)
   bool probing = false;   // path_probe: every bounce through the wavefront kernels
+  // rt_render_adaptive's later rounds: the pixels are the first list_n ids
+  // already in `wpix` (no tiles are dealt or staged), and the render continues
+  // the span rt_last_render_kernel_ms reports instead of starting a new one
+  bool from_list = false;
+  uint32_t list_n = 0;
 };
 
 // LDS stack ring (kLdsStack entries per lane) + global spill up to
@@ -389,9 +402,10 @@ int guard_render_report(rt_ctx* ctx, int nt) {
 }
 #endif
 
-// Wavefront render (wavefront.hip) of the tiles' pixels.  wave_layout.h
-// decides the schedule and where every twin's arrays lie; this allocates,
-// binds and launches.
+// Wavefront render (wavefront.hip) of the tiles' pixels, or (run.from_list)
+// of a pixel list that is already in `wpix`.  wave_layout.h decides the
+// schedule and where every twin's arrays lie; this allocates, binds and
+// launches.
 int render_wave(rt_ctx* ctx, const DCamera& dc, const rt_render_params* p, const std::vector<int4>& tiles, float* d_out,
                 const RenderRun& run) {
   hipStream_t st = run.st;
@@ -402,11 +416,16 @@ int render_wave(rt_ctx* ctx, const DCamera& dc, const rt_render_params* p, const
   // the knobs, the twins, and the pixel list dealt to them
   const WaveKnobs knobs = resolve_knobs(ctx->wopt, run.probing);
   const bool overlap = use_overlap(knobs, lit);
-  const int nt = choose_twins(knobs, ctx->dscene.shade_kind == SHADE_VOL, overlap, tile_pixels(tiles),
-                              p->samples_per_pixel, tiles.size());
+  if (run.from_list && run.list_n == 0) return RT_OK;   // an empty list launches nothing
+  const int nt = run.from_list
+                     ? choose_twins(knobs, ctx->dscene.shade_kind == SHADE_VOL, overlap, run.list_n,
+                                    p->samples_per_pixel, run.list_n)
+                     : choose_twins(knobs, ctx->dscene.shade_kind == SHADE_VOL, overlap, tile_pixels(tiles),
+                                    p->samples_per_pixel, tiles.size());
   uint32_t twin_npix[kMaxTwins];
-  deal_pixels(tiles, dc.width, nt, ctx->pix_host, twin_npix);
-  const uint32_t npix = uint32_t(ctx->pix_host.size());
+  if (run.from_list) split_list(run.list_n, nt, twin_npix);
+  else deal_pixels(tiles, dc.width, nt, ctx->pix_host, twin_npix);
+  const uint32_t npix = run.from_list ? run.list_n : uint32_t(ctx->pix_host.size());
   // path slots per batch, and the batch buffers: an automatic size that does
   // not fit after all is halved and tried again
   size_t target = knobs.slots;
@@ -434,13 +453,18 @@ int render_wave(rt_ctx* ctx, const DCamera& dc, const rt_render_params* p, const
   }
   // the other buffers
   const SpillLayout spill = spill_layout(nt, overlap, ctx->num_cus, spill_cap_for(int(ctx->dscene.stack_needed), kRing));
-  if ((rc = ensure(ctx, ctx->wpix, npix * sizeof(uint32_t)))) return rc;
+  if (run.from_list) {   // the list is there already: growing `wpix` now would lose it
+    if (!ctx->wpix.p || ctx->wpix.bytes < size_t(npix) * sizeof(uint32_t))
+      return set_err(ctx, RT_ERR_INVALID, "pixel list longer than its buffer");
+  } else if ((rc = ensure(ctx, ctx->wpix, npix * sizeof(uint32_t)))) {
+    return rc;
+  }
   if ((rc = ensure(ctx, ctx->wacc, size_t(npix) * 3 * sizeof(double)))) return rc;
   if (run.feat && (rc = ensure(ctx, ctx->wfacc, size_t(npix) * kFeatFloats * sizeof(double)))) return rc;
   if (run.mom_out && (rc = ensure(ctx, ctx->wmacc, size_t(npix) * kMomFloats * sizeof(double)))) return rc;
   if ((rc = ensure(ctx, ctx->counters, CNT_WORDS * sizeof(unsigned long long)))) return rc;
   if ((rc = ensure(ctx, ctx->wspill, spill.words() * sizeof(uint32_t)))) return rc;
-  if ((rc = stage_pixels(ctx, st))) return rc;
+  if (!run.from_list && (rc = stage_pixels(ctx, st))) return rc;
   if (count) HIPCHK(hipMemsetAsync(ctx->counters.p, 0, CNT_WORDS * sizeof(unsigned long long), st));
   if (overlap && (rc = ensure_overlap_streams(ctx))) return rc;
   // each twin's slices of those buffers, checked against what the buffers
@@ -509,7 +533,7 @@ int render_wave(rt_ctx* ctx, const DCamera& dc, const rt_render_params* p, const
     return rc;
   // fan out to the twins' streams, launch, join
   if (run.ms) HIPCHK(hipEventRecord(ctx->ev0, st));
-  HIPCHK(hipEventRecord(ctx->kev0, st));
+  if (!run.from_list) HIPCHK(hipEventRecord(ctx->kev0, st));
   if (nt > 1) {   // the other twins' streams start after the caller's stream reached here
     HIPCHK(hipEventRecord(ctx->twin_ev0, st));
     for (int t = 1; t < nt; ++t) HIPCHK(hipStreamWaitEvent(ctx->twin_st[t - 1], ctx->twin_ev0, 0));
@@ -818,6 +842,8 @@ void rt_ctx_destroy(rt_ctx* ctx) {
   free_buf(ctx->dn_work); free_buf(ctx->dn_in); free_buf(ctx->dn_feat); free_buf(ctx->dn_out);
   free_buf(ctx->wmacc); free_buf(ctx->mom);
   free_buf(ctx->dv_work); free_buf(ctx->dv_mom); free_buf(ctx->dv_var);
+  free_buf(ctx->ad_work); free_buf(ctx->ad_counts);
+  if (ctx->ad_pinned) (void)hipHostFree(ctx->ad_pinned);
   free_buf(ctx->frame); free_buf(ctx->frame_rgba); free_buf(ctx->frame_buckets);
   if (ctx->pix_pinned) (void)hipHostFree(ctx->pix_pinned);
   if (ctx->probe_pinned) (void)hipHostFree(ctx->probe_pinned);
@@ -1359,6 +1385,276 @@ int rt_render_moments_device(rt_ctx* ctx, const rt_camera_desc* cam, const rt_re
   RenderRun run{st};
   run.mom_out = moments_device;
   return render_impl(ctx, cam, params, accum_rgb_device, run);
+}
+
+// ---- adaptive sampling: rounds of the moments-mode render over the pixels
+// adaptive.hip's selection lists, until none is left or the budget is spent.
+static const char kAdaptiveMulti[] = "rt_render_adaptive on a multi-device context is not supported";
+
+int rt_adaptive_default_params(rt_adaptive_params* p) {
+  if (!p) return RT_ERR_INVALID;
+  p->min_spp = 16;
+  p->step_spp = 16;
+  p->neighbourhood = 1;
+  p->rel_error = 0.05f;
+  p->lum_floor = 0.01f;
+  return RT_OK;
+}
+
+namespace {
+
+int adaptive_check_params(rt_ctx* ctx, const rt_adaptive_params& ap, int32_t max_spp) {
+  if (ap.min_spp < 2) return set_err(ctx, RT_ERR_INVALID, "min_spp must be >= 2");
+  if (ap.step_spp < 1) return set_err(ctx, RT_ERR_INVALID, "step_spp must be >= 1");
+  if (ap.neighbourhood != 0 && ap.neighbourhood != 1) return set_err(ctx, RT_ERR_INVALID, "neighbourhood outside {0, 1}");
+  if (!std::isfinite(ap.rel_error) || !std::isfinite(ap.lum_floor) || ap.rel_error < 0.0f || ap.lum_floor < 0.0f)
+    return set_err(ctx, RT_ERR_INVALID, "rel_error / lum_floor must be finite and >= 0");
+  if (max_spp < 1) return set_err(ctx, RT_ERR_INVALID, "max_spp must be >= 1");
+  if ((int64_t(max_spp) - int64_t(ap.min_spp)) / int64_t(ap.step_spp) + 1 > 256)
+    return set_err(ctx, RT_ERR_INVALID, "more than 256 rounds possible");
+  return RT_OK;
+}
+
+// The context's working arrays for an image of n pixels (one allocation that
+// grows, like rt_denoise's), and `wpix` sized for a list of all of them: the
+// selection writes there, and a later ensure() would move it.
+struct AdWork {
+  uint32_t* counts;   // n: each pixel's samples so far (0: not in the call)
+  uint32_t* list;     // n: the call's pixels, as round 0 dealt them
+  uint32_t* blocks;   // grid: the selection's block counts
+  uint32_t* total;    // 1: the active list's length
+  uint8_t* flags;     // n
+  uint32_t grid;
+};
+
+int adaptive_buffers(rt_ctx* ctx, size_t n, AdWork& w) {
+  w.grid = ad_grid(n, ctx->num_cus);
+  const size_t words = 2 * n + w.grid + 4;
+  int rc;
+  if ((rc = ensure(ctx, ctx->ad_work, words * sizeof(uint32_t) + n))) return rc;
+  if ((rc = ensure(ctx, ctx->wpix, n * sizeof(uint32_t)))) return rc;
+  if (!ctx->ad_pinned) HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&ctx->ad_pinned), 4 * sizeof(uint32_t)));
+  w.counts = static_cast<uint32_t*>(ctx->ad_work.p);
+  w.list = w.counts + n;
+  w.blocks = w.list + n;
+  w.total = w.blocks + w.grid;
+  w.flags = reinterpret_cast<uint8_t*>(w.total + 4);
+  return RT_OK;
+}
+
+// One selection on `st` into `wpix`; waits for it: the host sizes the next
+// render by the list's length.
+int adaptive_select(rt_ctx* ctx, const float* d_mom, const AdWork& w, int32_t W, int32_t H, uint32_t max_spp,
+                    uint32_t cur, const rt_adaptive_params& ap, hipStream_t st, uint32_t* n_out) {
+  AdArgs a{};
+  a.moments = d_mom;
+  a.counts = w.counts;
+  a.flags = w.flags;
+  a.block_counts = w.blocks;
+  a.total = w.total;
+  a.list = static_cast<uint32_t*>(ctx->wpix.p);
+  a.w = W; a.h = H;
+  a.max_spp = max_spp;
+  a.cur = cur;
+  a.neighbourhood = ap.neighbourhood;
+  a.rel_error = ap.rel_error; a.lum_floor = ap.lum_floor;
+  HIPCHK(launch_adaptive_select(a, ctx->num_cus, st));
+  HIPCHK(hipMemcpyAsync(ctx->ad_pinned, w.total, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  *n_out = *ctx->ad_pinned;
+  if (size_t(*n_out) > size_t(W) * size_t(H)) return set_err(ctx, RT_ERR_DEVICE, "selection list longer than the image");
+  return RT_OK;
+}
+
+constexpr size_t kAdMaxPixels = size_t(1) << 31;   // pixel ids are 32-bit
+
+// The rounds, over device arrays on `st`.  Returns with the last round
+// enqueued; the callers wait for it.
+int adaptive_impl(rt_ctx* ctx, const rt_camera_desc* cam, const rt_render_params* p, const rt_adaptive_params* ap_in,
+                  float* d_accum, float* d_mom, uint32_t* d_counts, hipStream_t st, rt_adaptive_stats* stats) {
+  if (!ctx->has_scene) return set_err(ctx, RT_ERR_NO_SCENE, "no scene uploaded");
+  rt_adaptive_params ap;
+  rt_adaptive_default_params(&ap);
+  if (ap_in) ap = *ap_in;
+  const int32_t max_spp = p->samples_per_pixel;
+  int rc = adaptive_check_params(ctx, ap, max_spp);
+  if (rc) return rc;
+  if (p->max_depth < 0) return set_err(ctx, RT_ERR_INVALID, "bad depth");
+  if (p->sample_offset != 0 || p->accumulate != 0)
+    return set_err(ctx, RT_ERR_INVALID, "rt_render_adaptive takes sample_offset 0 and accumulate 0");
+  DCamera dc{};
+  if ((rc = make_camera(ctx, cam, dc))) return rc;
+  const size_t n = size_t(dc.width) * size_t(dc.height);
+  if (n > kAdMaxPixels) return set_err(ctx, RT_ERR_INVALID, "image too large");
+  std::vector<int4> tiles;
+  if ((rc = make_tiles(ctx, p, dc.width, dc.height, tiles))) return rc;
+  rt_adaptive_stats s{};
+  s.rounds = 1;
+  ctx->kev_recorded = false;
+  if (tiles.empty()) {
+    if (stats) *stats = s;
+    return RT_OK;
+  }
+  AdWork w{};
+  if ((rc = adaptive_buffers(ctx, n, w))) return rc;
+  HIPCHK(hipMemsetAsync(w.counts, 0, n * sizeof(uint32_t), st));
+  // round 0: the buckets' pixels, overwriting
+  rt_render_params q = *p;
+  uint32_t cur = uint32_t(std::min(ap.min_spp, max_spp));
+  q.samples_per_pixel = int32_t(cur);
+  RenderRun run{st};
+  run.mom_out = d_mom;
+  if ((rc = render_wave(ctx, dc, &q, tiles, d_accum, run))) return rc;
+  const uint32_t listed = uint32_t(ctx->pix_host.size());
+  HIPCHK(hipMemcpyAsync(w.list, ctx->wpix.p, size_t(listed) * sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
+  HIPCHK(launch_ad_set_counts(w.list, listed, w.counts, cur, ctx->num_cus, st));
+  s.samples = uint64_t(listed) * cur;
+  uint32_t active = listed;
+  // rounds r >= 1: the pixels still active, continuing their sample sequence
+  const std::vector<int4> none;
+  while (cur < uint32_t(max_spp)) {
+    if ((rc = adaptive_select(ctx, d_mom, w, dc.width, dc.height, uint32_t(max_spp), cur, ap, st, &active))) return rc;
+    if (active == 0) break;
+    const uint32_t step = std::min(uint32_t(ap.step_spp), uint32_t(max_spp) - cur);
+    q.samples_per_pixel = int32_t(step);
+    q.sample_offset = int32_t(cur);
+    q.accumulate = 1;
+    RenderRun more{st};
+    more.mom_out = d_mom;
+    more.from_list = true;
+    more.list_n = active;
+    if ((rc = render_wave(ctx, dc, &q, none, d_accum, more))) return rc;
+    HIPCHK(launch_ad_set_counts(static_cast<const uint32_t*>(ctx->wpix.p), active, w.counts, cur + step, ctx->num_cus, st));
+    cur += step;
+    s.samples += uint64_t(active) * step;
+    s.rounds += 1;
+  }
+  s.pixels_at_max = cur >= uint32_t(max_spp) ? int32_t(active) : 0;
+  HIPCHK(launch_ad_scatter_counts(w.list, listed, w.counts, d_counts, ctx->num_cus, st));
+  HIPCHK(hipEventRecord(ctx->kev1, st));   // the span covers every round and selection
+  ctx->kev_recorded = true;
+  if (stats) *stats = s;
+  return RT_OK;
+}
+
+// After the call's last work on `st` has finished: its span, device errors.
+int adaptive_finish(rt_ctx* ctx, rt_adaptive_stats* stats) {
+  int rc = check_render_error(ctx, true);
+  if (rc) return rc;
+  if (stats && ctx->kev_recorded) {
+    float f = 0.f;
+    HIPCHK(hipEventElapsedTime(&f, ctx->kev0, ctx->kev1));
+    stats->kernel_ms = f;
+  }
+  return RT_OK;
+}
+
+}  // namespace
+
+int rt_render_adaptive(rt_ctx* ctx, const rt_camera_desc* cam, const rt_render_params* params,
+                       const rt_adaptive_params* adaptive, float* accum_rgb, float* moments, uint32_t* counts,
+                       rt_adaptive_stats* stats) {
+  if (!ctx || !cam || !params || !accum_rgb || !moments || !counts) return RT_ERR_INVALID;
+  HIPCHK(hipSetDevice(ctx->device));
+  if (!ctx->subs.empty()) return set_err(ctx, RT_ERR_UNSUPPORTED, kAdaptiveMulti);
+  if (cam->image_width <= 0 || cam->image_height <= 0) return set_err(ctx, RT_ERR_INVALID, "bad image size");
+  if (!ctx->has_scene) return set_err(ctx, RT_ERR_NO_SCENE, "no scene uploaded");
+  const size_t n = size_t(cam->image_width) * cam->image_height;
+  int rc;
+  if ((rc = ensure(ctx, ctx->accum, n * 3 * sizeof(float)))) return rc;
+  if ((rc = ensure(ctx, ctx->mom, n * kMomFloats * sizeof(float)))) return rc;
+  if ((rc = ensure(ctx, ctx->ad_counts, n * sizeof(uint32_t)))) return rc;
+  hipStream_t st = ctx->stream;
+  HIPCHK(hipMemcpyAsync(ctx->accum.p, accum_rgb, n * 3 * sizeof(float), hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(ctx->mom.p, moments, n * kMomFloats * sizeof(float), hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(ctx->ad_counts.p, counts, n * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+  if ((rc = adaptive_impl(ctx, cam, params, adaptive, static_cast<float*>(ctx->accum.p), static_cast<float*>(ctx->mom.p),
+                          static_cast<uint32_t*>(ctx->ad_counts.p), st, stats)))
+    return rc;
+  HIPCHK(hipMemcpyAsync(accum_rgb, ctx->accum.p, n * 3 * sizeof(float), hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(moments, ctx->mom.p, n * kMomFloats * sizeof(float), hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(counts, ctx->ad_counts.p, n * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  return adaptive_finish(ctx, stats);
+}
+
+int rt_render_adaptive_device(rt_ctx* ctx, const rt_camera_desc* cam, const rt_render_params* params,
+                              const rt_adaptive_params* adaptive, float* accum_rgb_device, float* moments_device,
+                              uint32_t* counts_device, rt_adaptive_stats* stats, void* hip_stream) {
+  if (!ctx || !cam || !params || !accum_rgb_device || !moments_device || !counts_device) return RT_ERR_INVALID;
+  HIPCHK(hipSetDevice(ctx->device));
+  if (!ctx->subs.empty()) return set_err(ctx, RT_ERR_UNSUPPORTED, kAdaptiveMulti);
+  hipStream_t st = hip_stream ? static_cast<hipStream_t>(hip_stream) : ctx->stream;
+  int rc = check_render_error(ctx, false);
+  if (rc) return rc;
+  if ((rc = adaptive_impl(ctx, cam, params, adaptive, accum_rgb_device, moments_device, counts_device, st, stats)))
+    return rc;
+  HIPCHK(hipStreamSynchronize(st));
+  return adaptive_finish(ctx, stats);
+}
+
+int rt_adaptive_select(rt_ctx* ctx, const float* moments, const uint32_t* counts, int32_t width, int32_t height,
+                       int32_t max_spp, const rt_adaptive_params* params, uint32_t* list_out, uint32_t* n_out) {
+  if (!ctx || !moments || !counts || !list_out || !n_out) return RT_ERR_INVALID;
+  HIPCHK(hipSetDevice(ctx->device));
+  if (width <= 0 || height <= 0) return set_err(ctx, RT_ERR_INVALID, "bad image size");
+  rt_adaptive_params ap;
+  rt_adaptive_default_params(&ap);
+  if (params) ap = *params;
+  int rc = adaptive_check_params(ctx, ap, max_spp);
+  if (rc) return rc;
+  const size_t n = size_t(width) * size_t(height);
+  if (n > kAdMaxPixels) return set_err(ctx, RT_ERR_INVALID, "image too large");
+  AdWork w{};
+  if ((rc = adaptive_buffers(ctx, n, w))) return rc;
+  if ((rc = ensure(ctx, ctx->mom, n * kMomFloats * sizeof(float)))) return rc;
+  hipStream_t st = ctx->stream;
+  HIPCHK(hipMemcpyAsync(ctx->mom.p, moments, n * kMomFloats * sizeof(float), hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(w.counts, counts, n * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+  uint32_t m = 0;
+  if ((rc = adaptive_select(ctx, static_cast<const float*>(ctx->mom.p), w, width, height, uint32_t(max_spp), 0u, ap, st,
+                            &m)))
+    return rc;
+  if (m) HIPCHK(hipMemcpy(list_out, ctx->wpix.p, size_t(m) * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  *n_out = m;
+  return RT_OK;
+}
+
+static int normalize_check(rt_ctx* ctx, int32_t channels, int32_t width, int32_t height, int32_t target_spp) {
+  if (width <= 0 || height <= 0 || target_spp <= 0) return set_err(ctx, RT_ERR_INVALID, "bad image size or samples");
+  if (channels < 1 || channels > kAdMaxChannels) return set_err(ctx, RT_ERR_INVALID, "channels outside 1..8");
+  return RT_OK;
+}
+
+int rt_normalize_samples(rt_ctx* ctx, const float* sums, int32_t channels, const uint32_t* counts, int32_t width,
+                         int32_t height, int32_t target_spp, float* out) {
+  if (!ctx || !sums || !counts || !out) return RT_ERR_INVALID;
+  HIPCHK(hipSetDevice(ctx->device));
+  int rc = normalize_check(ctx, channels, width, height, target_spp);
+  if (rc) return rc;
+  const size_t n = size_t(width) * size_t(height);
+  if ((rc = ensure(ctx, ctx->dn_in, n * size_t(channels) * sizeof(float)))) return rc;
+  if ((rc = ensure(ctx, ctx->ad_counts, n * sizeof(uint32_t)))) return rc;
+  hipStream_t st = ctx->stream;
+  float* d = static_cast<float*>(ctx->dn_in.p);
+  HIPCHK(hipMemcpyAsync(d, sums, n * size_t(channels) * sizeof(float), hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(ctx->ad_counts.p, counts, n * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+  HIPCHK(launch_normalize(d, channels, static_cast<const uint32_t*>(ctx->ad_counts.p), n, target_spp, d, ctx->num_cus, st));
+  HIPCHK(hipMemcpyAsync(out, d, n * size_t(channels) * sizeof(float), hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  return RT_OK;
+}
+
+int rt_normalize_samples_device(rt_ctx* ctx, const float* sums_dev, int32_t channels, const uint32_t* counts_dev,
+                                int32_t width, int32_t height, int32_t target_spp, float* out_dev, void* hip_stream) {
+  if (!ctx || !sums_dev || !counts_dev || !out_dev) return RT_ERR_INVALID;
+  HIPCHK(hipSetDevice(ctx->device));
+  int rc = normalize_check(ctx, channels, width, height, target_spp);
+  if (rc) return rc;
+  hipStream_t st = hip_stream ? static_cast<hipStream_t>(hip_stream) : ctx->stream;
+  HIPCHK(launch_normalize(sums_dev, channels, counts_dev, size_t(width) * size_t(height), target_spp, out_dev,
+                          ctx->num_cus, st));
+  return RT_OK;
 }
 
 int rt_denoise_variance_default_params(rt_denoise_var_params* p) {

@@ -156,6 +156,18 @@ inline void deal_pixels(const std::vector<int4>& tiles, int width, int nt, std::
   }
 }
 
+// A pixel list that is already on the device (rt_render_adaptive's rounds)
+// is cut where it lies: twin t renders [n * t / nt, n * (t + 1) / nt).
+// choose_twins is fed the list's length for `ntiles`, so nt <= n and no part
+// is empty; an empty list has no parts (nothing is launched for it).
+inline void split_list(uint32_t n, int nt, uint32_t twin_npix[kMaxTwins]) {
+  for (int t = 0; t < kMaxTwins; ++t) twin_npix[t] = 0;
+  if (n == 0 || nt < 1) return;
+  nt = std::min(nt, kMaxTwins);
+  for (int t = 0; t < nt; ++t)
+    twin_npix[t] = uint32_t(uint64_t(n) * uint64_t(t + 1) / uint64_t(nt) - uint64_t(n) * uint64_t(t) / uint64_t(nt));
+}
+
 // ---- path slots per batch
 
 // Per slot: kSlotF4 float4 arrays (wavefront.h) + job info + visibility

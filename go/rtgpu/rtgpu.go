@@ -694,8 +694,96 @@ func (c *Ctx) DenoiseVariance(accum, feat, moments []float32, width, height, spp
 		(*C.rt_denoise_var_params)(unsafe.Pointer(&dp)), (*C.float)(unsafe.Pointer(&out[0])), vp))
 }
 
+// AdaptiveParams mirrors rt_adaptive_params.
+//
+//rtgpu:mirror rt_adaptive_params
+type AdaptiveParams struct {
+	MinSpp        int32   `c:"min_spp"`
+	StepSpp       int32   `c:"step_spp"`
+	Neighbourhood int32   `c:"neighbourhood"`
+	RelError      float32 `c:"rel_error"`
+	LumFloor      float32 `c:"lum_floor"`
+}
+
+// AdaptiveStats mirrors rt_adaptive_stats.
+//
+//rtgpu:mirror rt_adaptive_stats
+type AdaptiveStats struct {
+	KernelMs    float64 `c:"kernel_ms"`
+	Samples     uint64  `c:"samples"`
+	Rounds      int32   `c:"rounds"`
+	PixelsAtMax int32   `c:"pixels_at_max"`
+}
+
+// DefaultAdaptiveParams returns rt_adaptive_default_params.
+func DefaultAdaptiveParams() AdaptiveParams {
+	var p AdaptiveParams
+	C.rt_adaptive_default_params((*C.rt_adaptive_params)(unsafe.Pointer(&p)))
+	return p
+}
+
+// RenderAdaptive renders with p.SamplesPerPixel as the budget of every pixel
+// and stops sampling a pixel once the standard error of its mean luminance is
+// small enough (rt_render_adaptive); ap nil = the defaults.  accum
+// (Width*Height*3), moments (Width*Height*2) and counts (Width*Height) receive
+// the sums and moments of each bucket pixel's first counts[p] samples and
+// counts[p]; pixels outside the buckets are untouched.  p.SampleOffset must be
+// 0 and p.Accumulate false.  Blocks.
+func (c *Ctx) RenderAdaptive(cam *CameraDesc, p RenderParams, ap *AdaptiveParams, accum, moments []float32,
+	counts []uint32) (AdaptiveStats, error) {
+	var st AdaptiveStats
+	n := int(cam.ImageWidth) * int(cam.ImageHeight)
+	if len(accum) < n*3 || len(moments) < n*2 || len(counts) < n {
+		return st, &Error{StatusInvalid, "adaptive buffer too small"}
+	}
+	var pin runtime.Pinner
+	defer pin.Unpin()
+	prm := (*C.rt_render_params)(C.calloc(1, C.sizeof_rt_render_params))
+	defer C.free(unsafe.Pointer(prm))
+	prm.samples_per_pixel = C.int32_t(p.SamplesPerPixel)
+	prm.max_depth = C.int32_t(p.MaxDepth)
+	prm.sample_offset = C.int32_t(p.SampleOffset)
+	prm.seed = C.uint32_t(p.Seed)
+	if len(p.Buckets) > 0 {
+		pin.Pin(&p.Buckets[0])
+		prm.buckets = (*C.rt_bucket)(unsafe.Pointer(&p.Buckets[0]))
+		prm.num_buckets = C.int32_t(len(p.Buckets))
+	}
+	if p.Accumulate {
+		prm.accumulate = 1
+	}
+	dp := DefaultAdaptiveParams()
+	if ap != nil {
+		dp = *ap
+	}
+	rc := C.rt_render_adaptive(c.p, (*C.rt_camera_desc)(unsafe.Pointer(cam)), prm,
+		(*C.rt_adaptive_params)(unsafe.Pointer(&dp)), (*C.float)(unsafe.Pointer(&accum[0])),
+		(*C.float)(unsafe.Pointer(&moments[0])), (*C.uint32_t)(unsafe.Pointer(&counts[0])),
+		(*C.rt_adaptive_stats)(unsafe.Pointer(&st)))
+	return st, c.check(rc)
+}
+
+// NormalizeSamples turns sums over counts[p] samples per pixel (channels
+// floats each: 3 for a frame, 2 for moments, 8 for features) into sums over
+// targetSpp samples, (sums / counts) * targetSpp, which Tonemap, Denoise and
+// DenoiseVariance take (rt_normalize_samples).  out may be sums.
+func (c *Ctx) NormalizeSamples(sums []float32, channels int, counts []uint32, width, height, targetSpp int,
+	out []float32) error {
+	n := width * height
+	if n <= 0 || channels <= 0 || len(sums) < n*channels || len(counts) < n || len(out) < n*channels {
+		return &Error{StatusInvalid, "normalize buffer too small"}
+	}
+	return c.check(C.rt_normalize_samples(c.p, (*C.float)(unsafe.Pointer(&sums[0])), C.int32_t(channels),
+		(*C.uint32_t)(unsafe.Pointer(&counts[0])), C.int32_t(width), C.int32_t(height), C.int32_t(targetSpp),
+		(*C.float)(unsafe.Pointer(&out[0]))))
+}
+
 // Layout checks: each mirror is exactly as large as its C struct.
 var (
+	_ [unsafe.Sizeof(AdaptiveParams{}) - uintptr(C.sizeof_rt_adaptive_params)]byte
+	_ [uintptr(C.sizeof_rt_adaptive_params) - unsafe.Sizeof(AdaptiveParams{})]byte
+	_ [unsafe.Sizeof(AdaptiveStats{}) - uintptr(C.sizeof_rt_adaptive_stats)]byte
+	_ [uintptr(C.sizeof_rt_adaptive_stats) - unsafe.Sizeof(AdaptiveStats{})]byte
 	_ [unsafe.Sizeof(DenoiseVarParams{}) - uintptr(C.sizeof_rt_denoise_var_params)]byte
 	_ [uintptr(C.sizeof_rt_denoise_var_params) - unsafe.Sizeof(DenoiseVarParams{})]byte
 	_ [unsafe.Sizeof(DenoiseParams{}) - uintptr(C.sizeof_rt_denoise_params)]byte

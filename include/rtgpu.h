@@ -654,6 +654,97 @@ int rt_denoise_variance_device(rt_ctx* ctx, const float* accum_dev, const float*
                                int32_t width, int32_t height, int32_t spp, const rt_denoise_var_params* params,
                                float* out_dev, float* out_var_dev, void* hip_stream);
 
+/* Adaptive sampling: a render that stops sampling a pixel once the standard
+ * error of its mean luminance, estimated from its own samples, is small
+ * enough, and spends the samples where it is not.
+ * rt_render_params is read as for rt_render (seed, max_depth, buckets), with
+ * samples_per_pixel = max_spp, the budget a uniform render would spend on
+ * every pixel; sample_offset and accumulate must be 0.  adaptive NULL = the
+ * defaults.  accum_rgb (width*height*3), moments (width*height*2) and counts
+ * (width*height uint32) receive, for every pixel of the buckets, the sums and
+ * the moments of its first counts[p] samples (sample s is rt_render's sample
+ * s of that pixel: the same path key) and counts[p] itself; pixels outside
+ * the buckets are untouched in all three.
+ * The rounds:
+ *   round 0 is rt_render_moments of the buckets' pixels with min(min_spp,
+ *     max_spp) samples, offset 0, overwriting;
+ *   round r >= 1, with n the samples so far, first selects the active pixels
+ *     (below) and then is rt_render_moments over exactly those pixels with
+ *     min(step_spp, max_spp - n) samples, sample_offset n, accumulate 1;
+ *   a pixel that leaves the active set never returns, so every active pixel
+ *     holds the same n;
+ *   the call ends when no pixel is active or n = max_spp.
+ * A round's arithmetic is the render's own, so a pixel's final value is the
+ * chain float(double(previous) + fp64 sum of the round's samples), whichever
+ * other pixels were listed and whatever the schedule options.
+ * Selection, in fp32 with the operations as written (no fused multiply-add),
+ * from the pixel's moments m1, m2 and its n:
+ *   nf = float(n), mu = m1 / nf
+ *   var = max(0, m2 / nf - mu * mu) / (nf - 1)     (rt_denoise_variance's var_Y)
+ *   tol = rel_error * max(mu, lum_floor)
+ *   unconverged(p) = var > tol * tol
+ * neighbourhood 0: p stays active iff it is active and unconverged;
+ * neighbourhood 1: p stays active iff it is active and it, or one of its 8
+ * neighbours that is active, is unconverged.  Neighbours outside the image,
+ * outside the buckets or already dropped count as converged.  The dilation
+ * keeps the pixel whose first few samples all happened to agree next to
+ * pixels whose samples did not.  Stopping a pixel on the variance of its own
+ * samples makes its mean a biased estimator (pixels whose samples chance to
+ * agree stop early): the price of every such scheme.
+ * The selection runs on the device without atomics: the active list is in
+ * ascending pixel order and identical from run to run.
+ * Both variants block: the host reads each round's active count (4 bytes) to
+ * size the next render; rt_render_adaptive_device takes device arrays and
+ * saves the image copies, not the synchronisation.  rt_last_render_kernel_ms
+ * after either call covers the whole call.
+ * RT_ERR_INVALID: null pointers, min_spp < 2, step_spp < 1, neighbourhood
+ * outside {0, 1}, rel_error / lum_floor negative or not finite, max_spp < 1,
+ * more than 256 rounds possible ((max_spp - min_spp) / step_spp + 1 > 256),
+ * sample_offset or accumulate not 0.  RT_ERR_NO_SCENE as for rt_render.
+ * RT_ERR_UNSUPPORTED on a multi-device context, as for rt_render_moments.   */
+typedef struct rt_adaptive_params {
+  int32_t min_spp;        /* every listed pixel's first round; >= 2                  */
+  int32_t step_spp;       /* samples per later round; >= 1                           */
+  int32_t neighbourhood;  /* 0: a pixel's own estimate; 1: 3x3 dilation              */
+  float rel_error;        /* target standard error of the mean luminance, relative   */
+  float lum_floor;        /* ... to max(mean, lum_floor); >= 0                       */
+} rt_adaptive_params;
+typedef struct rt_adaptive_stats {
+  double kernel_ms;       /* the whole call's span on the stream                     */
+  uint64_t samples;       /* samples traced = sum of the listed pixels' counts       */
+  int32_t rounds;         /* renders run, >= 1                                       */
+  int32_t pixels_at_max;  /* listed pixels that stopped at max_spp, not by the test  */
+} rt_adaptive_stats;
+/* min_spp 16, step_spp 16, neighbourhood 1, rel_error 0.05, lum_floor 0.01
+ * (DESIGN.md "Adaptive sampling").                                          */
+int rt_adaptive_default_params(rt_adaptive_params* out);
+int rt_render_adaptive(rt_ctx* ctx, const rt_camera_desc* cam, const rt_render_params* params,
+                       const rt_adaptive_params* adaptive, float* accum_rgb, float* moments, uint32_t* counts,
+                       rt_adaptive_stats* stats);
+int rt_render_adaptive_device(rt_ctx* ctx, const rt_camera_desc* cam, const rt_render_params* params,
+                              const rt_adaptive_params* adaptive, float* accum_rgb_device, float* moments_device,
+                              uint32_t* counts_device, rt_adaptive_stats* stats, void* hip_stream);
+/* The selection step alone over host arrays (a probe, like rt_primary_hits;
+ * needs no scene): counts[p] == 0 = not in the call, counts[p] >= max_spp =
+ * done, every other pixel is active with n = counts[p].  Writes the ids
+ * (y * width + x) of the pixels that stay active to list_out (room for
+ * width*height) in ascending order, and their number to n_out.  params NULL =
+ * the defaults; refusals as above.                                          */
+int rt_adaptive_select(rt_ctx* ctx, const float* moments, const uint32_t* counts, int32_t width, int32_t height,
+                       int32_t max_spp, const rt_adaptive_params* params, uint32_t* list_out, uint32_t* n_out);
+/* An adaptive frame for the consumers that take one spp for the whole frame
+ * (rt_tonemap_rgba8, rt_denoise, rt_denoise_variance):
+ *   out[p][c] = (sums[p][c] / float(counts[p])) * float(target_spp)
+ * in fp32 in that order, for `channels` (1..8) floats per pixel; a pixel with
+ * counts[p] == 0 is copied bit for bit.  out may be sums.  Host arrays,
+ * blocks; the _device variant takes device arrays and is asynchronous on
+ * `hip_stream`.  RT_ERR_INVALID: null pointers, non-positive sizes or
+ * target_spp, channels outside 1..8.                                        */
+int rt_normalize_samples(rt_ctx* ctx, const float* sums, int32_t channels, const uint32_t* counts, int32_t width,
+                         int32_t height, int32_t target_spp, float* out);
+int rt_normalize_samples_device(rt_ctx* ctx, const float* sums_dev, int32_t channels, const uint32_t* counts_dev,
+                                int32_t width, int32_t height, int32_t target_spp, float* out_dev, void* hip_stream);
+
 #ifdef __cplusplus
 }
 #endif
