@@ -168,8 +168,23 @@ __device__ __forceinline__ TRay make_tray(V3 o, V3 d) {
 //     operands, same operations, bit-identical t0/t1);
 //   * the narrowing is fmaxf/fminf, which also return the other operand for
 //     a NaN (v_max/v_min, max3/min3 chains);
-//   * one final tmax > tmin test, equivalent to the per-axis early exits
-//     because the bounds only narrow.
+//   * one final test, equivalent to the per-axis early exits because the
+//     bounds only narrow;
+//   * that test is tmax >= tmin, not the reference's tmax > tmin.  A flat
+//     primitive's box is 2e-4 thick; once half an ulp of |plane - o| exceeds
+//     1e-4 both of its planes round to one t and the interval collapses to
+//     tmax == tmin, though the box is not empty.  Subtracting o and
+//     multiplying by one inv are monotone, so for lo <= hi the near plane
+//     never rounds above the far plane: equality means "collapsed", and an
+//     unused child (lo = +inf, hi = -inf) or a NaN stays rejected.  Every
+//     slab test in trav_step follows the same rule;
+//   * one equality is not a collapse: +inf == +inf.  A ray with a direction
+//     component of exactly 0 that lies outside the slab on its near side has
+//     both planes of that axis at +inf, and with no hit yet tmax is +inf too.
+//     That box is missed (tmax is capped at FLT_MAX below; the 4-wide slab
+//     returns its entry t = +inf, which is its "missed" value).  The 8-wide
+//     test keeps such a child: its scenes hold no RotateX / RotateZ box,
+//     every box contains its geometry, and the visit finds nothing.
 __device__ __forceinline__ bool box_hit(float x0, float x1, float y0, float y1, float z0, float z1,
                                         const TRay& r, float tmin, float tmax, float& tnear) {
   const bool sx = r.inv.x < 0.0f, sy = r.inv.y < 0.0f, sz = r.inv.z < 0.0f;
@@ -177,9 +192,10 @@ __device__ __forceinline__ bool box_hit(float x0, float x1, float y0, float y1, 
   const float ty0 = ((sy ? y1 : y0) - r.o.y) * r.inv.y, ty1 = ((sy ? y0 : y1) - r.o.y) * r.inv.y;
   const float tz0 = ((sz ? z1 : z0) - r.o.z) * r.inv.z, tz1 = ((sz ? z0 : z1) - r.o.z) * r.inv.z;
   tmin = fmaxf(fmaxf(fmaxf(tmin, tx0), ty0), tz0);
-  tmax = fminf(fminf(fminf(tmax, tx1), ty1), tz1);
+  // (the cap: tmax stays below +inf, so tmin = +inf misses; it rides in the second min3)
+  tmax = fminf(fminf(fminf(tmax, tx1), ty1), fminf(tz1, 3.402823466e+38f));
   tnear = tmin;
-  return tmax > tmin;
+  return tmax >= tmin;
 }
 
 // ----------------------------------------------------------------------------
@@ -945,7 +961,7 @@ __device__ __forceinline__ int trav_step(const DScene& sc, Trav& T, const TStack
       if (!exact) return v;
       --T.sp;
       const float te = __uint_as_float(S.pop(T.sp));
-      if (te < best_t(T)) return v;   // BVHNode.Hit's box test against the closest hit so far
+      if (te <= best_t(T)) return v;   // BVHNode.Hit's box test against the closest hit so far (box_hit's >= rule)
     }
   };
   // The host bounds the stack need (flatten: stack_needed <= kStackMax), so an
@@ -1014,7 +1030,7 @@ __device__ __forceinline__ int trav_step(const DScene& sc, Trav& T, const TStack
         const uint32_t nz = c < 4 ? rz.x : rz.y, fz = c < 4 ? rz.z : rz.w;
         const float tn = fmaxf(fmaxf(fmaxf(T.tmin, fmaf(qf(nx), bx, ax)), fmaf(qf(ny), by, ay)), fmaf(qf(nz), bz, az));
         const float tf = fminf(fminf(fminf(hi, fmaf(qf(fx), bx, ax)), fmaf(qf(fy), by, ay)), fmaf(qf(fz), bz, az));
-        m |= (tf > tn ? 1u : 0u) << (uint32_t(c) ^ oct);
+        m |= (tf >= tn ? 1u : 0u) << (uint32_t(c) ^ oct);
       }
       if (kCount) cnt.nodes++;
       const uint32_t imask = (h1.z >> 8) & 0xFFu, lmask = h1.z & 0xFFu, twomask = h1.w & 0xFFu;
@@ -1049,7 +1065,7 @@ __device__ __forceinline__ int trav_step(const DScene& sc, Trav& T, const TStack
     auto slab = [&](float tx0, float tx1, float ty0, float ty1, float tz0, float tz1) {
       const float a = fmaxf(fmaxf(fmaxf(T.tmin, tx0), ty0), tz0);
       const float b = fminf(fminf(fminf(hi, tx1), ty1), tz1);
-      return b > a ? a : inf;
+      return b >= a ? a : inf;
     };
     if (kQuant) {
       // Quantised node (DNodeQ, 64 B; 32-bit byte offsets from the uniform

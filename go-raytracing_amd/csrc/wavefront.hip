@@ -488,7 +488,11 @@ __device__ __forceinline__ void shade_path(const DScene& sc, const DCamera& cam,
                 V3 ct = scale(mul(scale(em, cth / pdfL * w), att), float(nl));
                 ca = mk(gomin(ct.x, 20.0f), gomin(ct.y, 20.0f), gomin(ct.z, 20.0f));
                 da = ldir;
-                tmax_a = dist - 0.001f;
+                // camera.go:639's dist - 0.001 keeps the light out of its own shadow ray.  In fp32
+                // that rounds back to dist from dist >= 16384 (and is within the light's own
+                // rounding from a few thousand units on), so the end also stays 2^-20 of dist
+                // short: >= 8 ulps, and below 0.001 (no change) for dist < 1048
+                tmax_a = fminf(dist - 0.001f, dist * 0.99999905f);
                 flags |= 1u;
               }
             }

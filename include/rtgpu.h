@@ -316,6 +316,20 @@ int rt_last_dealing(const rt_ctx* ctx, int32_t* tiles, int32_t* runs, int32_t ma
  *     without RotateX/RotateZ, circles or volumes left in the world BVH and
  *     whose BLASes are host-built (not RT_BLAS_DEVICE); others keep
  *     RT_NODES_FP32.  Hits equal the fp32 format's within the same envelope.
+ *     Scale and ray distance, every format and both world-BVH builders: a
+ *     box whose slab interval collapses in fp32 (a flat primitive's 2e-4
+ *     box seen from >= 2048 units away, or lying at a coordinate >= 2048) is
+ *     kept, not culled (tmax >= tmin).  Pinned by
+ *     tests/test_scale_host.py and tests/test_gpu_scale.py: first hits equal
+ *     the float64 reference arithmetic's for scenes 8 to 524,288 units across,
+ *     up to 16 scene sizes from the origin, with ray origins up to 64 scene
+ *     sizes outside the scene and axis-parallel rays.  An area light's
+ *     shadow ray ends at min(dist - 0.001, dist * (1 - 2^-20)): the reference's
+ *     dist - 0.001 (camera.go:639) where fp32 resolves it (unchanged below
+ *     dist = 1048), and still short of the light where it does not.  Radiance
+ *     at scene coordinates beyond about 8192 keeps a bias of a few percent
+ *     against float64: the ray offset 0.001 at a ray's start is then below
+ *     half an ulp of the hit point.
  *   RT_OPT_VOLUMES: RT_VOLUMES_LIFTED (default) = Volume objects are kept
  *     out of the world BVH and tested by the shading kernel on every path
  *     ray and NEE shadow ray (same results: the volume test runs over the

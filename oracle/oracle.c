@@ -162,6 +162,8 @@ static void oscene_free(OScene* os) {
 #define BOX_LO(x) (x)
 #define BOX_HI(x) (x)
 #define TRI_P_BARY 0
+#define BOX_MISS(mx, mn) ((mx) <= (mn))   /* aabb.go: tmax <= tmin */
+#define SHADOW_END(dist) ((dist) - 0.001)  /* camera.go:639 */
 #include "oracle_impl.h"
 #undef REAL
 #undef SUF
@@ -180,6 +182,8 @@ static void oscene_free(OScene* os) {
 #undef BOX_LO
 #undef BOX_HI
 #undef TRI_P_BARY
+#undef BOX_MISS
+#undef SHADOW_END
 
 /* ------------------------------------------------------------ fp32 instantiation */
 static inline float o_pow5f(float x) { float x2 = x * x; return (x2 * x2) * x; }
@@ -235,6 +239,10 @@ static inline float o_round_up(double x) {
 #define BOX_LO(x) o_round_down(x)
 #define BOX_HI(x) o_round_up(x)
 #define TRI_P_BARY 1
+/* the device's rule: a collapsed interval (==) is kept, +inf == +inf (an axis-parallel ray beside the slab) is not */
+#define BOX_MISS(mx, mn) ((mx) < (mn) || (mn) == INFINITY)
+/* the device's rule (wavefront.hip): also 2^-20 of dist short of the light, where fp32 no longer resolves 0.001 */
+#define SHADOW_END(dist) fminf((dist) - 0.001f, (dist) * 0.99999905f)
 #include "oracle_impl.h"
 
 /* ------------------------------------------------------------ public API */

@@ -17,6 +17,17 @@
  *
  * Two arithmetic modes: fp64 (the reference's float64, "reference mode")
  * and fp32 (operation-for-operation mirror of the GPU kernels).
+ *
+ * The two modes differ in two rules besides the arithmetic.  AABB.Hit:  fp64
+ * keeps Go's "tmax <= tmin -> miss" (aabb.go).  fp32 follows the device
+ * (device_common.h box_hit): "tmax < tmin -> miss", because in fp32 the two
+ * planes of a 2e-4-thick box round to one t once the ray origin is ~2048
+ * units away, and that collapsed interval is not an empty one.
+ * And in the far end of an area light's shadow ray: fp64 keeps Go's
+ * dist - 0.001 (camera.go:639); fp32 follows the device's
+ * min(dist - 0.001, dist * (1 - 2^-20)), which is the same value below
+ * dist = 1048 and keeps the light out of its own shadow ray where fp32 no
+ * longer resolves 0.001.
  */
 #ifndef RT_ORACLE_H
 #define RT_ORACLE_H

@@ -178,7 +178,9 @@ static inline void FN(set_face)(FN(Rec)* rec, FN(Ray) r, V3R out) {             
   rec->N = rec->front ? out : FN(neg)(out);
 }
 
-/* AABB.Hit aabb.go:59-116 */
+/* AABB.Hit aabb.go:59-116.  BOX_MISS: fp64 is Go's tmax <= tmin; fp32 is the
+ * device's tmax < tmin (device_common.h box_hit: in fp32 a thin box's two
+ * planes can round to one t, and the collapsed interval is not empty). */
 static int FN(aabb_hit)(const REAL* b, FN(Ray) r, REAL mn, REAL mx) {
   const REAL o[3] = {r.o.x, r.o.y, r.o.z}, dd[3] = {r.d.x, r.d.y, r.d.z};
   for (int a = 0; a < 3; ++a) {
@@ -188,7 +190,7 @@ static int FN(aabb_hit)(const REAL* b, FN(Ray) r, REAL mn, REAL mx) {
     if (adinv < 0) { REAL s = t0; t0 = t1; t1 = s; }
     if (t0 > mn) mn = t0;
     if (t1 < mx) mx = t1;
-    if (mx <= mn) return 0;
+    if (BOX_MISS(mx, mn)) return 0;
   }
   return 1;
 }
@@ -640,7 +642,7 @@ static V3R FN(sample_lights)(FN(TC)* c, const FN(Rec)* rec, V3R rdir, V3R att) {
         FN(Ray) sr;
         sr.o = rec->P; sr.d = ldir; sr.tm = 0;
         FN(Rec) srec;
-        const int occluded = FN(world_hit)(c, O_DOM_VOL_SH_AREA, sr, (REAL)0.001, dist - (REAL)0.001, &srec);
+        const int occluded = FN(world_hit)(c, O_DOM_VOL_SH_AREA, sr, (REAL)0.001, SHADOW_END(dist), &srec);
         if (c->r_nee && (int)c->bounce < c->r_nb &&                         /* path recorder: a ray whose */
             !(FABS(FN(dot)(FN(mk)(p[12], p[13], p[14]), FN(neg)(ldir))) < (REAL)0.001))   /* light term counts */
           c->r_nee[(size_t)c->bounce * c->r_npix + c->r_pix] |= 1 | (occluded ? 0 : 4);

@@ -36,20 +36,13 @@ struct EmuScene {
   ~EmuScene() { if (scn) rts_scene_destroy(scn); }
 };
 
-// Returns 0 on success, else an exit code (message on stderr).
-static int load(const char* name, int width, const char* asset_dir, EmuScene& E) {
-  rts_scene_options opt{};
-  opt.width = width;
-  opt.lucy_rings = 60;
-  opt.lucy_cols = 80;
-  if (getenv("RTG_EMU_FULL_LUCY")) opt.lucy_rings = opt.lucy_cols = 0;   // the scene's own 280K-triangle mesh
-  opt.asset_dir = asset_dir;
-  char err[512] = {0};
-  if (rts_scene_create(name, &opt, &E.scn, err, sizeof err) != 0) { fprintf(stderr, "%s\n", err); return 3; }
+// The caller's description, flattened with `fo` (TLAS / BLAS builder, node
+// format: what rt_ctx_set_option selects on a context).  The description is
+// only read during the call.  Returns 0 on success, else an exit code
+// (message on stderr).
+static int load_desc(const rt_scene_desc* desc, const rt_camera_desc* c, const FlattenOptions& fo, EmuScene& E) {
   std::string ferr;
-  FlattenOptions fo;
-  if (const char* nf = getenv("RTG_EMU_QUANT")) fo.quant_nodes = atoi(nf);   // node format under test
-  if (flatten_scene(rts_scene_get_desc(E.scn), E.h, ferr, fo)) { fprintf(stderr, "%s\n", ferr.c_str()); return 4; }
+  if (flatten_scene(desc, E.h, ferr, fo)) { fprintf(stderr, "%s\n", ferr.c_str()); return 4; }
   const HostScene& h = E.h;
   DScene& d = E.d;
   auto pad = [&](const auto& v) {
@@ -120,7 +113,6 @@ static int load(const char* name, int width, const char* asset_dir, EmuScene& E)
   E.vol_recs = build_vol_recs(h);
   d.vol_recs = E.vol_recs.empty() ? nullptr : E.vol_recs.data();
 
-  const rt_camera_desc* c = rts_scene_get_camera(E.scn);
   DCamera& cam = E.cam;
   for (int a = 0; a < 3; ++a) {
     cam.center[a] = float(c->center[a]); cam.pixel00[a] = float(c->pixel00[a]);
@@ -133,6 +125,22 @@ static int load(const char* name, int width, const char* asset_dir, EmuScene& E)
   cam.width = c->image_width; cam.height = c->image_height;
   E.max_depth = c->max_depth;
   return 0;
+}
+
+// A librtscene scene by name.  Returns 0 on success, else an exit code
+// (message on stderr).
+static int load(const char* name, int width, const char* asset_dir, EmuScene& E) {
+  rts_scene_options opt{};
+  opt.width = width;
+  opt.lucy_rings = 60;
+  opt.lucy_cols = 80;
+  if (getenv("RTG_EMU_FULL_LUCY")) opt.lucy_rings = opt.lucy_cols = 0;   // the scene's own 280K-triangle mesh
+  opt.asset_dir = asset_dir;
+  char err[512] = {0};
+  if (rts_scene_create(name, &opt, &E.scn, err, sizeof err) != 0) { fprintf(stderr, "%s\n", err); return 3; }
+  FlattenOptions fo;
+  if (const char* nf = getenv("RTG_EMU_QUANT")) fo.quant_nodes = atoi(nf);   // node format under test
+  return load_desc(rts_scene_get_desc(E.scn), rts_scene_get_camera(E.scn), fo, E);
 }
 
 }  // namespace emu

@@ -1,0 +1,76 @@
+// emu_trace.h — test-only: one ray through the production closest-hit kernel
+// (wavefront.hip k_extend, a later bounce: the ray read from the path stream)
+// on the host, one lane.  Include after wavefront.hip and emu_scene.h
+// (tests/ray_emu.cpp, tests/hits_emu.cpp).
+#pragma once
+#include <vector>
+
+namespace emu {
+
+using namespace rtg;
+
+constexpr int kTraceRing = 8;
+
+// The buffers k_extend reads and writes for one path slot, and the WaveArgs
+// over them.
+struct TraceArgs {
+  std::vector<float4> f4 = std::vector<float4>(size_t(kSlotF4), float4{0.0f, 0.0f, 0.0f, 0.0f});
+  std::vector<uint32_t> q = std::vector<uint32_t>(CNT_WORDS_Q, 0u), sj = std::vector<uint32_t>(2, 0u);
+  std::vector<uint32_t> pixels = std::vector<uint32_t>(1, 0u);
+  std::vector<uint32_t> spill = std::vector<uint32_t>(size_t(kStackMax - kTraceRing), 0u);
+  std::vector<double> acc = std::vector<double>(3, 0.0);
+  std::vector<unsigned long long> counters = std::vector<unsigned long long>(3 * CNT_BLOCK, 0ull);
+  int err = 0;
+  WaveArgs a{};
+
+  explicit TraceArgs(int max_depth) {
+    auto arr = [&](int k) { return &f4[size_t(k)]; };
+    for (int k = 0; k < 2; ++k) a.s[k] = PathStream{arr(3 * k), arr(3 * k + 1), arr(3 * k + 2)};
+    a.hit = arr(6); a.Lout = arr(7);
+    a.sj_p = arr(8); a.sj_a = arr(9); a.sj_h = arr(10);
+    a.ne_a = arr(11); a.ne_h = arr(12); a.ne_beta = arr(13);
+    a.counts = q.data();
+    a.sj_info = sj.data();
+    a.sj_vis = sj.data() + 1;
+    a.pixels = pixels.data();
+    a.npix = 1;
+    a.acc = acc.data();
+    a.max_depth = max_depth;
+    a.counters = counters.data();
+    a.err = &err;
+    a.refill = 1;
+    a.spill = spill.data();
+    a.spill_lanes = 1;
+    a.spill_cap = kStackMax - kTraceRing;
+    a.slots = 1;
+    a.out_pixels = 1;
+  }
+  TraceArgs(const TraceArgs&) = delete;
+  TraceArgs& operator=(const TraceArgs&) = delete;
+};
+
+template <bool kWide, bool kQuant>
+static float4 trace_variant(const DScene& sc, const DCamera& cam, WaveArgs a, float4 o, float4 d) {
+  a.s[0].o[0] = o;
+  a.s[0].d[0] = d;
+  a.s[0].beta[0] = float4{1.0f, 1.0f, 1.0f, 0.0f};
+  a.counts[CNT_STREAM0] = 1u;
+  for (uint32_t k = 0; k < kSegs; ++k) a.counts[CNT_FETCH_EXT + k * kSegStride] = 0u;
+  k_extend<kTraceRing, false, false, false, kQuant, kWide>(sc, cam, a, a.s[0], a.counts + CNT_STREAM0,
+                                                           a.counts + CNT_STREAM1, a.counts + CNT_SHADOW,
+                                                           a.counts + CNT_FETCH_SH, a.counts + CNT_FETCH_EXT, 0u);
+  return a.hit[0];
+}
+
+// The hit record k_extend stores (store_hit: t, kind << 28 | idx, instance,
+// TLAS ref position) for the ray (o, d), in the kernel variant of the
+// scene's node format.
+static float4 trace_one(const EmuScene& E, TraceArgs& T, const float* o, const float* d) {
+  const float4 ro{o[0], o[1], o[2], 0.0f}, rd{d[0], d[1], d[2], 0.0f};
+  const DScene& sc = E.d;
+  return sc.wide_nodes ? trace_variant<true, false>(sc, E.cam, T.a, ro, rd)
+         : sc.quant_nodes ? trace_variant<false, true>(sc, E.cam, T.a, ro, rd)
+                          : trace_variant<false, false>(sc, E.cam, T.a, ro, rd);
+}
+
+}  // namespace emu

@@ -46,6 +46,20 @@ def fp32_bar(name, gpu_sum, ref_sum, spp):
     assert off <= (FP32_OFF_HDRI if name.startswith("hdri") else FP32_OFF), f"{name}: {off:.3e} of the pixels off"
     return mse, off
 
+FP64_MSE, FP64_BIAS = 1e-4, 2e-3
+
+
+def fp64_bar(name, gpu_sum, ref_sum, spp, mse_max=FP64_MSE, bias_max=FP64_BIAS):
+    """(mse, relative bias) against the oracle's float64 mode; asserts the fp64 bar."""
+    a, b = gpu_sum.astype(np.float64) / spp, ref_sum / spp
+    mse = float(np.mean((a - b) ** 2))
+    bias = float((a.mean() - b.mean()) / max(b.mean(), 1e-6))
+    print(f"fp64 tolerance {name} {a.shape[1]}x{a.shape[0]} {spp}spp: mse {mse:.3e} rel_bias {bias:+.2e}")
+    assert mse <= mse_max, f"{name}: mse {mse:.3e}"
+    assert abs(bias) <= bias_max, f"{name}: relative bias {bias:+.3e}"
+    return mse, bias
+
+
 LUCY = dict(lucy_rings=60, lucy_cols=80)
 SCENES = [
     ("simple", dict(width=96)),
@@ -179,13 +193,7 @@ def test_radiance_vs_fp64_reference(g, O, ctx, name, kw, spp):
     p = g.make_params(spp, cam.max_depth, seed=5)
     gpu, _ = ctx.render(cam, p)
     ref = O.render(s.desc, cam, p, fp32=False, threads=16)
-    a = gpu.astype(np.float64) / spp
-    b = ref / spp
-    mse = float(np.mean((a - b) ** 2))
-    bias = float((a.mean() - b.mean()) / max(b.mean(), 1e-6))
-    print(f"fp64 tolerance {name} {cam.image_width}x{cam.image_height} {spp}spp: mse {mse:.3e} rel_bias {bias:+.2e}")
-    assert mse <= 1e-4, f"{name}: mse {mse:.3e}"
-    assert abs(bias) <= 2e-3, f"{name}: relative bias {bias:+.3e}"
+    fp64_bar(name, gpu, ref, spp)
 
 
 def test_tonemap_bit_exact(g, O, ctx):

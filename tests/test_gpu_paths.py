@@ -58,18 +58,22 @@ def compare_paths(g, O, name, kw, samples, bounces=0, volumes=LIFTED, nodes="fp3
     """Per bounce and sample: (alive paths, compared, diverged, id/t mismatches,
     NEE mismatches).  Raises nothing; the caller asserts."""
     s = g.Scene(name, **kw)
-    cam = s.camera
+    return compare_desc_paths(g, O, s.desc, s.camera, samples, bounces, volumes, nodes)
+
+
+def compare_desc_paths(g, O, desc, cam, samples, bounces=0, volumes=LIFTED, nodes="fp32"):
+    """compare_paths over a caller's description and camera."""
     nb = bounces or cam.max_depth
     c = g.Context(0)
     rows = []
     try:
         c.set_option(g.RT_OPT_VOLUMES, g.RT_VOLUMES_IN_BVH if volumes == IN_BVH else g.RT_VOLUMES_LIFTED)
         c.set_node_format(nodes)
-        c.upload(s.desc)
+        c.upload(desc)
         assert c.info().node_format == {"fp32": g.RT_NODES_FP32, "wide8": g.RT_NODES_WIDE8}[nodes]
         lifted = c.info().volumes > 0
         for sample in samples:
-            ot, op, ott, oray, onee = O.path_records(s.desc, cam, SEED, sample, nb, fp32=True, threads=16)
+            ot, op, ott, oray, onee = O.path_records(desc, cam, SEED, sample, nb, fp32=True, threads=16)
             for b in range(nb):
                 if not np.any(ot[b] != -2):   # no path left on the oracle's side: the GPU must agree
                     gt = c.extend_hits(cam, SEED, sample, b)[0]
