@@ -46,6 +46,7 @@ STATUS = {0: "RT_OK", -1: "RT_ERR_INVALID", -2: "RT_ERR_UNSUPPORTED", -3: "RT_ER
 # hittable kinds (rtgpu.h)
 RT_SPHERE, RT_QUAD, RT_TRIANGLE, RT_PLANE, RT_LIST, RT_BVH_NODE, RT_BVH_LEAF = 1, 2, 3, 4, 5, 6, 7
 RT_TRANSLATE, RT_ROTATE_X, RT_ROTATE_Y, RT_ROTATE_Z, RT_SCALE, RT_VOLUME = 8, 9, 10, 11, 12, 13
+RT_CIRCLE = 14
 RT_LAMBERTIAN, RT_METAL, RT_DIELECTRIC, RT_DIFFUSE_LIGHT, RT_ISOTROPIC = 1, 2, 3, 4, 5
 RT_TEX_SOLID, RT_TEX_CHECKER, RT_TEX_NOISE, RT_TEX_IMAGE = 1, 2, 3, 4
 

@@ -454,9 +454,10 @@ __device__ bool volume_hit(const DScene& sc, const DVolume& vol, V3 wo, V3 wd, f
   // (a sphere's slot holds its index as an exact float value, not a bit
   // pattern: below 2^24 every index is exact and no denormal is involved)
   if (n <= kCache && sc.n_spheres < (1u << 24)) {
-    // Only the two closest distances matter, and a quad's / triangle's hit
-    // distance does not depend on the interval's lower bound (quad_t / tri_t
-    // test it last): each is intersected once, with the bound -inf, and both
+    // Only the two closest distances matter, and a quad's / triangle's /
+    // circle's hit distance does not depend on the interval's lower bound
+    // (quad_t / tri_t / circle_t only compare against it): each is
+    // intersected once, with the bound -inf, and both
     // passes filter the cached distances (the same values the two-pass loop
     // below computes, so the same t1, t2).  Spheres pick their root by the
     // bound and are intersected per pass.
@@ -471,6 +472,7 @@ __device__ bool volume_hit(const DScene& sc, const DVolume& vol, V3 wo, V3 wd, f
       bool ok = false;
       if (pk == PK_QUAD) ok = quad_t(sc.quads[GIX(pi, sc.n_quads, 5)], o, d, ninf, tq[k]);
       else if (pk == PK_TRI) ok = tri_t(sc.tris[GIX(pi, sc.n_tris, 6)], o, d, ninf, tq[k]);
+      else if (pk == PK_CIRCLE) ok = circle_t(sc.circles[GIX(pi, sc.n_circles, 36)], o, d, ninf, tq[k]);
       else if (pk == PK_SPHERE) { sph |= 1u << k; tq[k] = float(pi); }
       if (ok) valid |= 1u << k;
     }
@@ -504,6 +506,7 @@ __device__ bool volume_hit(const DScene& sc, const DVolume& vol, V3 wo, V3 wd, f
       bool ok = false;
       if (pk == PK_QUAD) { ok = quad_t(sc.quads[GIX(pi, sc.n_quads, 5)], o, d, lo, t) && t <= closest; }
       else if (pk == PK_TRI) { ok = tri_t(sc.tris[GIX(pi, sc.n_tris, 6)], o, d, lo, t) && t <= closest; }
+      else if (pk == PK_CIRCLE) { ok = circle_t(sc.circles[GIX(pi, sc.n_circles, 36)], o, d, lo, t) && t <= closest; }
       else if (pk == PK_SPHERE) { ok = sphere_t(sc.spheres[GIX(pi, sc.n_spheres, 7)], o, d, time, lo, t) && t < closest; }
       if (ok) { closest = t; found = true; }
     }

@@ -110,6 +110,13 @@ static int load_desc(const rt_scene_desc* desc, const rt_camera_desc* c, const F
   d.num_vol_refs = int32_t(h.vol_refs.size());
   d.has_volumes = h.volumes.size() > h.vol_refs.size() ? 1 : 0;
   if (d.num_vol_refs > 0) d.shade_kind = SHADE_VOL;
+  // tables beyond LDS: the full variant reads them from global memory
+  // (api.cpp upload_one; lifted volumes with such tables are its internal error)
+  if (h.materials.size() > size_t(kLdsMaterials) || h.textures.size() > size_t(kLdsTextures) ||
+      h.lights.size() > size_t(kLdsLights)) {
+    if (d.shade_kind == SHADE_VOL) { fprintf(stderr, "lifted volumes with tables beyond LDS\n"); return 5; }
+    d.shade_kind = SHADE_FULL;
+  }
   E.vol_recs = build_vol_recs(h);
   d.vol_recs = E.vol_recs.empty() ? nullptr : E.vol_recs.data();
 

@@ -3,6 +3,7 @@
 // on the host, one lane.  Include after wavefront.hip and emu_scene.h
 // (tests/ray_emu.cpp, tests/hits_emu.cpp).
 #pragma once
+#include <cstring>
 #include <vector>
 
 namespace emu {
@@ -49,16 +50,24 @@ struct TraceArgs {
   TraceArgs& operator=(const TraceArgs&) = delete;
 };
 
-template <bool kWide, bool kQuant>
-static float4 trace_variant(const DScene& sc, const DCamera& cam, WaveArgs a, float4 o, float4 d) {
+// key: the path's RNG key (d.w of the stream's ray); bounce: the path's
+// bounce as the stream carries it (beta.w bits 16..30), which only the
+// rare-primitive variant (kVol: volumes in the world BVH) reads.
+template <bool kWide, bool kQuant, bool kVol = false>
+static float4 trace_variant(const DScene& sc, const DCamera& cam, WaveArgs a, float4 o, float4 d, uint32_t key = 0u,
+                            uint32_t bounce = 0u) {
+  const uint32_t bw = (bounce & 0x7FFFu) << 16;
+  float bwf;
+  std::memcpy(&d.w, &key, 4);
+  std::memcpy(&bwf, &bw, 4);
   a.s[0].o[0] = o;
   a.s[0].d[0] = d;
-  a.s[0].beta[0] = float4{1.0f, 1.0f, 1.0f, 0.0f};
+  a.s[0].beta[0] = float4{1.0f, 1.0f, 1.0f, bwf};
   a.counts[CNT_STREAM0] = 1u;
   for (uint32_t k = 0; k < kSegs; ++k) a.counts[CNT_FETCH_EXT + k * kSegStride] = 0u;
-  k_extend<kTraceRing, false, false, false, kQuant, kWide>(sc, cam, a, a.s[0], a.counts + CNT_STREAM0,
-                                                           a.counts + CNT_STREAM1, a.counts + CNT_SHADOW,
-                                                           a.counts + CNT_FETCH_SH, a.counts + CNT_FETCH_EXT, 0u);
+  k_extend<kTraceRing, false, kVol, false, kQuant, kWide>(sc, cam, a, a.s[0], a.counts + CNT_STREAM0,
+                                                          a.counts + CNT_STREAM1, a.counts + CNT_SHADOW,
+                                                          a.counts + CNT_FETCH_SH, a.counts + CNT_FETCH_EXT, 0u);
   return a.hit[0];
 }
 
@@ -71,6 +80,21 @@ static float4 trace_one(const EmuScene& E, TraceArgs& T, const float* o, const f
   return sc.wide_nodes ? trace_variant<true, false>(sc, E.cam, T.a, ro, rd)
          : sc.quant_nodes ? trace_variant<false, true>(sc, E.cam, T.a, ro, rd)
                           : trace_variant<false, false>(sc, E.cam, T.a, ro, rd);
+}
+
+// The same for a path's ray at a given bounce, in the variant
+// launch_wavefront picks for the scene: the rare-primitive kernels when a
+// volume is left in the world BVH, a circle exists or the scene traverses in
+// reference order (they have no 8-wide form), else the node format's own.
+static float4 trace_path(const EmuScene& E, TraceArgs& T, const float* o, const float* d, uint32_t key, uint32_t bounce) {
+  const float4 ro{o[0], o[1], o[2], 0.0f}, rd{d[0], d[1], d[2], 0.0f};
+  const DScene& sc = E.d;
+  if (sc.has_volumes != 0 || sc.n_circles > 0 || sc.dfs_order != 0)
+    return sc.quant_nodes ? trace_variant<false, true, true>(sc, E.cam, T.a, ro, rd, key, bounce)
+                          : trace_variant<false, false, true>(sc, E.cam, T.a, ro, rd, key, bounce);
+  return sc.wide_nodes ? trace_variant<true, false>(sc, E.cam, T.a, ro, rd, key, bounce)
+         : sc.quant_nodes ? trace_variant<false, true>(sc, E.cam, T.a, ro, rd, key, bounce)
+                          : trace_variant<false, false>(sc, E.cam, T.a, ro, rd, key, bounce);
 }
 
 }  // namespace emu

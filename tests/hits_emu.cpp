@@ -6,7 +6,12 @@
 // tests/ray_emu.cpp, but the scene is an rt_scene_desc, the flatten options
 // are the caller's, and the hit record is mapped to hittable ids the way
 // probe.hip's path_hits_kernel maps it (rt_primary_hits' conventions: top,
-// prim = -1 and t = -1 for a miss).  Not a product path.
+// prim = -1 and t = -1 for a miss).  hits_emu_run takes rays without a path
+// (no RNG key: scenes whose hits draw random numbers, volumes, are refused);
+// hits_emu_run_paths takes a path's rays with their pixel and bounce and
+// runs volume scenes too, in either placement (tests/test_volume_host.py),
+// and hits_emu_placement reports where the flattener put the volumes.  Not a
+// product path.
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -64,6 +69,93 @@ extern "C" int hits_emu_run(const rt_scene_desc* desc, const rt_camera_desc* cam
     if (w[1] != 0u) {
       hit_ids(sc, int(w[1] >> 28), int(w[1] & 0x0FFFFFFFu), int(w[3]), top[i], prim[i]);
       t[i] = h.x;
+    }
+  }
+  return T.err ? 6 : 0;
+}
+
+// Where flatten_scene puts the scene's volumes and what the upload derives
+// from that (tests/test_volume_host.py).  out[0..7]: num_vol_refs,
+// has_volumes, shade_kind, the number of DVolRec records, needs_uv, whether
+// the rare-primitive kernels run, the node format used, volumes in all.
+// codes[rec * kVolRecQuads + k]: record quad k's axis code (0: a general
+// quad, or none); ntests[rec]: the record's test count.  Returns 0, or
+// load_desc's code.
+extern "C" int hits_emu_placement(const rt_scene_desc* desc, const rt_camera_desc* cam, int lift_volumes, int node_format,
+                                  int32_t* out, uint32_t* codes, int32_t* ntests) {
+  emu::EmuScene E;
+  FlattenOptions fo;
+  fo.quant_nodes = node_format;
+  fo.lift_volumes = lift_volumes;
+  if (int rc = emu::load_desc(desc, cam, fo, E)) return rc;
+  const DScene& sc = E.d;
+  out[0] = sc.num_vol_refs;
+  out[1] = sc.has_volumes;
+  out[2] = sc.shade_kind;
+  out[3] = int32_t(E.vol_recs.size());
+  out[4] = sc.needs_uv;
+  out[5] = (sc.has_volumes != 0 || sc.n_circles > 0 || sc.dfs_order != 0) ? 1 : 0;
+  out[6] = sc.wide_nodes ? 2 : sc.quant_nodes ? 1 : 0;
+  out[7] = int32_t(sc.n_volumes);
+  for (int i = 0; i < kVolRecMax * kVolRecQuads; ++i) codes[i] = 0u;
+  for (int i = 0; i < kVolRecMax; ++i) ntests[i] = 0;
+  for (size_t r = 0; r < E.vol_recs.size() && r < size_t(kVolRecMax); ++r) {
+    ntests[r] = E.vol_recs[r].ref.ntests;
+    for (int k = 0; k < E.vol_recs[r].nq && k < kVolRecQuads; ++k)
+      memcpy(&codes[r * kVolRecQuads + size_t(k)], &E.vol_recs[r].q[k].pad0, 4);
+  }
+  return 0;
+}
+
+// flatten_scene's status for the description (RT_OK or an rt_status), the
+// message on stderr: the refusals.
+extern "C" int hits_emu_flatten_status(const rt_scene_desc* desc, int lift_volumes) {
+  HostScene h;
+  std::string err;
+  FlattenOptions fo;
+  fo.lift_volumes = lift_volumes;
+  const int rc = flatten_scene(desc, h, err, fo);
+  if (rc) fprintf(stderr, "hits_emu: flatten: %s\n", err.c_str());
+  return rc;
+}
+
+// Closest hits of n path rays at bounce `bounce` (pix[i]: the path's pixel;
+// the RNG key is production's for (seed, pixel, sample)), as the pipeline
+// finds them: k_extend in the variant launch_wavefront picks (volumes left in
+// the world BVH are tested there), then the lifted volumes' test as k_shade
+// and the path probe apply it (lifted_volumes).  Any scene the flattener
+// takes.  lift_volumes: RT_VOLUMES_LIFTED (1) or RT_VOLUMES_IN_BVH (0).
+// Returns as hits_emu_run.
+extern "C" int hits_emu_run_paths(const rt_scene_desc* desc, const rt_camera_desc* cam, int tlas_builder, int node_format,
+                                  int lift_volumes, uint32_t seed, uint32_t sample, int bounce, const int32_t* pix,
+                                  const float* o, const float* d, int n, int32_t* top, int32_t* prim, float* t,
+                                  int32_t* format_used) {
+  emu::EmuScene E;
+  FlattenOptions fo;
+  fo.tlas_builder = tlas_builder;
+  fo.quant_nodes = node_format;
+  fo.lift_volumes = lift_volumes;
+  if (int rc = emu::load_desc(desc, cam, fo, E)) return rc;
+  const DScene& sc = E.d;
+  *format_used = sc.wide_nodes ? 2 : sc.quant_nodes ? 1 : 0;
+  emu::TraceArgs T(E.max_depth);
+  for (int i = 0; i < n; ++i) {
+    const uint32_t key = path_key(seed, uint32_t(pix[i]), sample);
+    const float4 h = emu::trace_path(E, T, o + 3 * i, d + 3 * i, key, uint32_t(bounce));
+    uint32_t w[4];
+    memcpy(w, &h, 16);
+    uint32_t kh = w[1];
+    float ht = h.x;
+    int hinst = int(w[2]), hrefpos = int(w[3]);
+    Cnt cnt = {};
+    if (sc.num_vol_refs > 0)
+      lifted_volumes<false>(sc, mk(o[3 * i], o[3 * i + 1], o[3 * i + 2]), mk(d[3 * i], d[3 * i + 1], d[3 * i + 2]), key,
+                            uint32_t(bounce), kh, ht, hinst, hrefpos, cnt, sc.vol_recs);
+    top[i] = prim[i] = -1;
+    t[i] = -1.0f;
+    if (kh != 0u) {
+      hit_ids(sc, int(kh >> 28), int(kh & 0x0FFFFFFFu), hrefpos, top[i], prim[i]);
+      t[i] = ht;
     }
   }
   return T.err ? 6 : 0;

@@ -13,8 +13,24 @@ class Builder:
         self.mats = []
         self.texs = []
         self.lights = []
+        self.images = []
 
     # materials / textures -------------------------------------------------
+    def image_texture(self, width, height, rgb):
+        """ImageTexture (image_texture.go:5-41) over a width x height image of
+        linear rgb triples, row-major."""
+        px = np.ascontiguousarray(rgb, np.float64).reshape(height, width, 3)
+        self.images.append(px)
+        t = self.g.RtTexture(self.g.RT_TEX_IMAGE, -1, -1, (C.c_double * 3)(0, 0, 0), 0.0, 0.0, -1, len(self.images) - 1)
+        self.texs.append(t)
+        return len(self.texs) - 1
+
+    def pad_tables(self, n):
+        """n more Lambertian materials, each with a solid texture of its own,
+        that nothing refers to (table size only)."""
+        for i in range(n):
+            self.lambertian((0.25, 0.5, 0.75))
+
     def solid(self, rgb):
         t = self.g.RtTexture(self.g.RT_TEX_SOLID, -1, -1, (C.c_double * 3)(*rgb), 0.0)
         self.texs.append(t)
@@ -81,6 +97,31 @@ class Builder:
         lo, hi = pts.min(0), pts.max(0)
         return self._add(self.g.RT_TRIANGLE, mat, 0, 0, self._pad([lo[0], hi[0], lo[1], hi[1], lo[2], hi[2]]),
                          list(a) + list(b) + list(c) + list(n))
+
+    def circle(self, c, n, r, mat):
+        """Circle (circle.go:14-31): centre, unit normal, radius, D = n . c."""
+        c, n = np.array(c, float), np.array(n, float)
+        n = n / np.linalg.norm(n)
+        lo, hi = c - r, c + r
+        return self._add(self.g.RT_CIRCLE, mat, 0, 0, self._pad([lo[0], hi[0], lo[1], hi[1], lo[2], hi[2]]),
+                         list(c) + list(n) + [r, float(n @ c)])
+
+    def box_quads(self, lo, hi, mat, swap=False):
+        """The six faces of the box [lo, hi] as quads, in the order -x +x -y +y
+        -z +z.  Face on axis k: u along axis k + 1 and v along k + 2 (cyclic),
+        or the other way round with swap (the normal u x v then points along
+        -k: Quad.Hit faces it to the ray either way)."""
+        lo, hi = np.array(lo, float), np.array(hi, float)
+        out = []
+        for k in range(3):
+            for side in (lo, hi):
+                Q = lo.copy()
+                Q[k] = side[k]
+                u, v = np.zeros(3), np.zeros(3)
+                u[(k + 1) % 3] = (hi - lo)[(k + 1) % 3]
+                v[(k + 2) % 3] = (hi - lo)[(k + 2) % 3]
+                out.append(self.quad(Q, v, u, mat) if swap else self.quad(Q, u, v, mat))
+        return out
 
     def plane(self, p, n, mat):
         n = np.array(n, float)
@@ -164,6 +205,13 @@ class Builder:
         d.lights = C.cast(self._larr, C.POINTER(C.c_int32))
         d.num_lights = len(self.lights)
         d.environment = None
+        if self.images:
+            self._iarr = (self.g.RtImage * len(self.images))()
+            for i, px in enumerate(self.images):
+                self._iarr[i].height, self._iarr[i].width = px.shape[:2]
+                self._iarr[i].rgb = px.ctypes.data_as(C.POINTER(C.c_double))
+            d.images = C.cast(self._iarr, C.POINTER(self.g.RtImage))
+            d.num_images = len(self.images)
         self._desc = d
         return d
 

@@ -61,8 +61,12 @@ def compare_paths(g, O, name, kw, samples, bounces=0, volumes=LIFTED, nodes="fp3
     return compare_desc_paths(g, O, s.desc, s.camera, samples, bounces, volumes, nodes)
 
 
-def compare_desc_paths(g, O, desc, cam, samples, bounces=0, volumes=LIFTED, nodes="fp32"):
-    """compare_paths over a caller's description and camera."""
+def compare_desc_paths(g, O, desc, cam, samples, bounces=0, volumes=LIFTED, nodes="fp32", nodes_taken=None,
+                       every_shadow_ray=False):
+    """compare_paths over a caller's description and camera.  nodes_taken: the
+    node format the scene must report (default: the one asked for);
+    every_shadow_ray: the traced flags must equal the oracle's even though the
+    scene has volumes (the caller knows that none is lifted)."""
     nb = bounces or cam.max_depth
     c = g.Context(0)
     rows = []
@@ -70,8 +74,9 @@ def compare_desc_paths(g, O, desc, cam, samples, bounces=0, volumes=LIFTED, node
         c.set_option(g.RT_OPT_VOLUMES, g.RT_VOLUMES_IN_BVH if volumes == IN_BVH else g.RT_VOLUMES_LIFTED)
         c.set_node_format(nodes)
         c.upload(desc)
-        assert c.info().node_format == {"fp32": g.RT_NODES_FP32, "wide8": g.RT_NODES_WIDE8}[nodes]
-        lifted = c.info().volumes > 0
+        assert c.info().node_format == {"fp32": g.RT_NODES_FP32, "quant8": g.RT_NODES_QUANT8,
+                                        "wide8": g.RT_NODES_WIDE8}[nodes_taken or nodes]
+        lifted = c.info().volumes > 0 and not every_shadow_ray
         for sample in samples:
             ot, op, ott, oray, onee = O.path_records(desc, cam, SEED, sample, nb, fp32=True, threads=16)
             for b in range(nb):
