@@ -10,8 +10,9 @@
 // (no RNG key: scenes whose hits draw random numbers, volumes, are refused);
 // hits_emu_run_paths takes a path's rays with their pixel and bounce and
 // runs volume scenes too, in either placement (tests/test_volume_host.py),
-// and hits_emu_placement reports where the flattener put the volumes.  Not a
-// product path.
+// and hits_emu_placement reports where the flattener put the volumes;
+// hits_emu_shade follows the closest hit with the production shade_path and
+// returns what it decides (tests/test_shade_kat.py).  Not a product path.
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -156,6 +157,121 @@ extern "C" int hits_emu_run_paths(const rt_scene_desc* desc, const rt_camera_des
     if (kh != 0u) {
       hit_ids(sc, int(kh >> 28), int(kh & 0x0FFFFFFFu), hrefpos, top[i], prim[i]);
       t[i] = ht;
+    }
+  }
+  return T.err ? 6 : 0;
+}
+
+namespace {
+
+struct ShadeOut {
+  int32_t* cont; float* P; float* sd; float* nbeta; float* Ladd; uint32_t* flags;
+  float* ca; float* da; float* tmax_a; float* ch; float* dh;
+};
+
+void put3(float* dst, int i, const V3& v) { dst[3 * i] = v.x; dst[3 * i + 1] = v.y; dst[3 * i + 2] = v.z; }
+
+template <bool kEnvIS, int kShade, bool kFirst>
+void shade_one(const emu::EmuScene& E, emu::TraceArgs& T, float4 h, V3 ro, V3 rd, V3 beta, uint32_t key, int dleft,
+               uint32_t bounce, bool allow, int i, const ShadeOut& out) {
+  bool cont = false, want_shadow = false, lout_set = false;
+  uint32_t flags = 0, nstate = 0;
+  float tmax_a = 0.0f;
+  V3 P = mk(0.0f, 0.0f, 0.0f), sd = P, nbeta = P, ca = P, ch = P, da = P, dh = P;
+  Cnt cnt = {};
+  T.a.Lout[0] = float4{0.0f, 0.0f, 0.0f, 0.0f};
+  shade_path<false, kEnvIS, kShade, kFirst>(E.d, E.cam, T.a, E.d.vol_recs, h, ro, rd, beta, key, 0u, dleft, bounce, allow,
+                                            cont, want_shadow, flags, nstate, tmax_a, P, sd, nbeta, ca, ch, da, dh,
+                                            lout_set, cnt);
+  out.cont[i] = cont ? 1 : 0;
+  out.flags[i] = want_shadow ? flags : 0u;
+  out.tmax_a[i] = tmax_a;
+  put3(out.P, i, P); put3(out.sd, i, sd); put3(out.nbeta, i, nbeta); put3(out.ca, i, ca); put3(out.da, i, da);
+  put3(out.ch, i, ch); put3(out.dh, i, dh);
+  const float4 L = T.a.Lout[0];
+  put3(out.Ladd, i, lout_set ? mk(L.x, L.y, L.z) : mk(0.0f, 0.0f, 0.0f));
+}
+
+template <bool kEnvIS, bool kFirst, class... A>
+void shade_by_kind(int shade, A&&... args) {
+  if (shade == SHADE_FULL) shade_one<kEnvIS, SHADE_FULL, kFirst>(args...);
+  else if (shade == SHADE_VOL) shade_one<kEnvIS, SHADE_VOL, kFirst>(args...);
+  else if (shade == SHADE_MAT) shade_one<kEnvIS, SHADE_MAT, kFirst>(args...);
+  else shade_one<kEnvIS, SHADE_LEAN, kFirst>(args...);
+}
+
+}  // namespace
+
+// How the flattener hands the environment's texels to the device: 1 RGBE
+// words (every texel re-encodes exactly), 0 fp32 texels, -1 no environment;
+// or -(10 + load_desc's code).
+extern "C" int hits_emu_env_format(const rt_scene_desc* desc, const rt_camera_desc* cam) {
+  emu::EmuScene E;
+  FlattenOptions fo;
+  if (int rc = emu::load_desc(desc, cam, fo, E)) return -(10 + rc);
+  if (!E.d.env.valid) return -1;
+  return E.d.env.rgbe ? 1 : 0;
+}
+
+// One bounce of n paths through the production pipeline's two halves: the
+// closest hit as hits_emu_run_paths finds it (k_extend, one lane), then
+// shade_path in the variant run_variant picks for the scene (shade_kind, the
+// importance-sampled HDRI only beside a light, kFirst at bounce 0), with a
+// one-slot Lout.  Per path: seed / sample / pix[i] key it, (o, d, beta) are
+// its incoming ray and throughput, dleft the depth left, allow whether an
+// emitter it hits counts (camera.go:477).  o == NULL (bounce 0 only): the
+// camera ray is made by the production get_ray for pixel pix[i] and returned
+// in ray (n * 6).  Out: hit (0 miss) and t of the closest hit; cont (a
+// scattered ray goes on: P, sd, nbeta); Ladd, the radiance the bounce added
+// (beta * miss colour or emission); flags (bit 0 / 1: the area / HDRI shadow
+// ray wanted) with ca, da, tmax_a and ch, dh, the NEE contributions and
+// directions (tests/test_shade_kat.py).  Returns as hits_emu_run.
+extern "C" int hits_emu_shade(const rt_scene_desc* desc, const rt_camera_desc* cam, int node_format, uint32_t seed,
+                              uint32_t sample, int bounce, int dleft, int allow, const int32_t* pix, const float* o,
+                              const float* d, const float* beta, int n, float* ray, int32_t* hit, float* t, int32_t* cont,
+                              float* P, float* sd, float* nbeta, float* Ladd, uint32_t* flags, float* ca, float* da,
+                              float* tmax_a, float* ch, float* dh) {
+  emu::EmuScene E;
+  FlattenOptions fo;
+  fo.quant_nodes = node_format;
+  if (int rc = emu::load_desc(desc, cam, fo, E)) return rc;
+  if (!o && bounce != 0) return 2;
+  const DScene& sc = E.d;
+  const bool envis = sc.env.valid && sc.env.use_is && sc.num_lights > 0;   // run_variant
+  emu::TraceArgs T(E.max_depth);
+  const ShadeOut out{cont, P, sd, nbeta, Ladd, flags, ca, da, tmax_a, ch, dh};
+  for (int i = 0; i < n; ++i) {
+    const uint32_t key = path_key(seed, uint32_t(pix[i]), sample);
+    V3 ro, rd;
+    if (o) {
+      ro = mk(o[3 * i], o[3 * i + 1], o[3 * i + 2]);
+      rd = mk(d[3 * i], d[3 * i + 1], d[3 * i + 2]);
+    } else {
+      float time;
+      get_ray(E.cam, pix[i] % E.cam.width, pix[i] / E.cam.width, key, ro, rd, time);
+    }
+    if (ray) { put3(ray, 2 * i, ro); put3(ray, 2 * i + 1, rd); }
+    const float fo3[3] = {ro.x, ro.y, ro.z}, fd3[3] = {rd.x, rd.y, rd.z};
+    const float4 h = emu::trace_path(E, T, fo3, fd3, key, uint32_t(bounce));
+    uint32_t w[4];
+    memcpy(w, &h, 16);
+    {   // the hit reported: with the lifted volumes' test applied, as shade_path applies it to its own copy
+      uint32_t kh = w[1];
+      float ht = h.x;
+      int hinst = int(w[2]), hrefpos = int(w[3]);
+      Cnt c0 = {};
+      if (sc.num_vol_refs > 0) lifted_volumes<false>(sc, ro, rd, key, uint32_t(bounce), kh, ht, hinst, hrefpos, c0, sc.vol_recs);
+      hit[i] = kh != 0u ? 1 : 0;
+      t[i] = kh != 0u ? ht : -1.0f;
+    }
+    const V3 b = mk(beta[3 * i], beta[3 * i + 1], beta[3 * i + 2]);
+    const uint32_t bn = uint32_t(bounce);
+    if (envis) {
+      if (bounce == 0) shade_by_kind<true, true>(sc.shade_kind, E, T, h, ro, rd, b, key, dleft, bn, allow != 0, i, out);
+      else shade_by_kind<true, false>(sc.shade_kind, E, T, h, ro, rd, b, key, dleft, bn, allow != 0, i, out);
+    } else {
+      if (bounce == 0) shade_by_kind<false, true>(sc.shade_kind, E, T, h, ro, rd, b, key, dleft, bn, allow != 0, i, out);
+      else shade_by_kind<false, false>(sc.shade_kind, E, T, h, ro, rd, b, key, dleft, bn, allow != 0, i, out);
     }
   }
   return T.err ? 6 : 0;

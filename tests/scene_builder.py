@@ -14,6 +14,8 @@ class Builder:
         self.texs = []
         self.lights = []
         self.images = []
+        self.perlins = []
+        self.env = None
 
     # materials / textures -------------------------------------------------
     def image_texture(self, width, height, rgb):
@@ -24,6 +26,31 @@ class Builder:
         t = self.g.RtTexture(self.g.RT_TEX_IMAGE, -1, -1, (C.c_double * 3)(0, 0, 0), 0.0, 0.0, -1, len(self.images) - 1)
         self.texs.append(t)
         return len(self.texs) - 1
+
+    def noise_texture(self, scale, randvec, perm_x, perm_y, perm_z):
+        """NoiseTexture (texture.go:81-85) over a Perlin generator of its own
+        (noise.go:8-13): 256 unit vectors and three permutations of 0..255."""
+        p = self.g.RtPerlin()
+        for i in range(256):
+            for a in range(3):
+                p.randvec[i][a] = float(randvec[i][a])
+            p.perm_x[i], p.perm_y[i], p.perm_z[i] = int(perm_x[i]), int(perm_y[i]), int(perm_z[i])
+        self.perlins.append(p)
+        t = self.g.RtTexture(self.g.RT_TEX_NOISE, -1, -1, (C.c_double * 3)(0, 0, 0), 0.0, float(scale),
+                             len(self.perlins) - 1, -1)
+        self.texs.append(t)
+        return len(self.texs) - 1
+
+    def environment(self, rgb, rotation=0.0, importance=False):
+        """HDRIEnvironment (hdri.go:13-26) over a (height, width, 3) float64
+        array; rotation in radians."""
+        self.env = (np.ascontiguousarray(rgb, np.float64), float(rotation), bool(importance))
+
+    def metal(self, albedo, fuzz):
+        return self.mat(self.g.RT_METAL, albedo=albedo, fuzz=fuzz)
+
+    def dielectric(self, ior):
+        return self.mat(self.g.RT_DIELECTRIC, ior=ior)
 
     def pad_tables(self, n):
         """n more Lambertian materials, each with a solid texture of its own,
@@ -205,6 +232,15 @@ class Builder:
         d.lights = C.cast(self._larr, C.POINTER(C.c_int32))
         d.num_lights = len(self.lights)
         d.environment = None
+        if self.env is not None:
+            px, rot, imp = self.env
+            self._env = self.g.RtEnvironment(px.shape[1], px.shape[0], px.ctypes.data_as(C.POINTER(C.c_double)), rot,
+                                             1 if imp else 0)
+            d.environment = C.pointer(self._env)
+        if self.perlins:
+            self._parr = (self.g.RtPerlin * len(self.perlins))(*self.perlins)
+            d.perlins = C.cast(self._parr, C.POINTER(self.g.RtPerlin))
+            d.num_perlins = len(self.perlins)
         if self.images:
             self._iarr = (self.g.RtImage * len(self.images))()
             for i, px in enumerate(self.images):
@@ -223,4 +259,14 @@ def pinhole(g, w, h, origin, pixel00, du, dv, max_depth=5, sky=False, bg=(0, 0, 
         c.center[i], c.pixel00[i], c.pixel_delta_u[i], c.pixel_delta_v[i] = origin[i], pixel00[i], du[i], dv[i]
         c.background[i] = bg[i]
     c.use_sky_gradient = 1 if sky else 0
+    return c
+
+
+def defocus_pinhole(g, w, h, origin, pixel00, du, dv, angle, disk_u, disk_v, **kw):
+    """pinhole with a lens: defocus_angle > 0 and the disk's two axes
+    (camera.go:341-343, 380-384)."""
+    c = pinhole(g, w, h, origin, pixel00, du, dv, **kw)
+    c.defocus_angle = angle
+    for i in range(3):
+        c.defocus_disk_u[i], c.defocus_disk_v[i] = disk_u[i], disk_v[i]
     return c
