@@ -12,15 +12,19 @@
 // runs volume scenes too, in either placement (tests/test_volume_host.py),
 // and hits_emu_placement reports where the flattener put the volumes;
 // hits_emu_shade follows the closest hit with the production shade_path and
-// returns what it decides (tests/test_shade_kat.py).  Not a product path.
+// returns what it decides (tests/test_shade_kat.py); hits_emu_render runs the
+// whole wavefront pipeline (wave_run.h) over the description and returns the
+// frame (tests/test_path_kat.py).  Not a product path.
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <vector>
 
 #include "../go-raytracing_amd/csrc/wavefront.hip"
+#include "../go-raytracing_amd/csrc/wave_layout.h"
 #include "emu_scene.h"
 #include "emu_trace.h"
+#include "wave_run.h"
 
 using namespace rtg;
 
@@ -275,4 +279,27 @@ extern "C" int hits_emu_shade(const rt_scene_desc* desc, const rt_camera_desc* c
     }
   }
   return T.err ? 6 : 0;
+}
+
+// One frame of the description through the production wavefront pipeline on
+// the host (wave_run.h: camera -> extend -> shade -> shadow -> NEE apply ->
+// accumulate -> finalize, the kernel variants run_variant picks, one batch):
+// spp samples from sample_offset to `depth` (rt_render_params), the camera's
+// own max_depth kept for the phantom-HDRI rule.  out: H * W * 3 float sums,
+// what rt_render returns.  volumes_in_bvh: RT_OPT_VOLUMES' value,
+// RT_VOLUMES_LIFTED (0) or RT_VOLUMES_IN_BVH (1).  Returns 0, load_desc's code, or
+// 6 when a kernel flagged an internal error.
+extern "C" int hits_emu_render(const rt_scene_desc* desc, const rt_camera_desc* cam, int node_format, uint32_t seed,
+                               uint32_t sample_offset, int spp, int depth, float* out, int volumes_in_bvh) {
+  emu::EmuScene E;
+  FlattenOptions fo;
+  fo.quant_nodes = node_format;
+  fo.lift_volumes = volumes_in_bvh ? 0 : 1;
+  if (int rc = emu::load_desc(desc, cam, fo, E)) return rc;
+  const DScene& sc = E.d;
+  const bool envis = sc.env.valid && sc.env.use_is && sc.num_lights > 0;   // run_variant
+  std::vector<float> frame;
+  const int err = wave_run::render(E, seed, sample_offset, uint32_t(spp), uint32_t(spp), depth, envis, frame, nullptr);
+  memcpy(out, frame.data(), frame.size() * sizeof(float));
+  return err ? 6 : 0;
 }
