@@ -14,7 +14,9 @@
 // hits_emu_shade follows the closest hit with the production shade_path and
 // returns what it decides (tests/test_shade_kat.py); hits_emu_render runs the
 // whole wavefront pipeline (wave_run.h) over the description and returns the
-// frame (tests/test_path_kat.py).  Not a product path.
+// frame (tests/test_path_kat.py), hits_emu_render_opts the same with the
+// world-BVH builder named and the node format taken reported
+// (tests/test_xform_kat.py).  Not a product path.
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -289,14 +291,31 @@ extern "C" int hits_emu_shade(const rt_scene_desc* desc, const rt_camera_desc* c
 // what rt_render returns.  volumes_in_bvh: RT_OPT_VOLUMES' value,
 // RT_VOLUMES_LIFTED (0) or RT_VOLUMES_IN_BVH (1).  Returns 0, load_desc's code, or
 // 6 when a kernel flagged an internal error.
+extern "C" int hits_emu_render_opts(const rt_scene_desc* desc, const rt_camera_desc* cam, int node_format, int tlas_builder,
+                                    uint32_t seed, uint32_t sample_offset, int spp, int depth, float* out,
+                                    int volumes_in_bvh, int32_t* format_used);
+
 extern "C" int hits_emu_render(const rt_scene_desc* desc, const rt_camera_desc* cam, int node_format, uint32_t seed,
                                uint32_t sample_offset, int spp, int depth, float* out, int volumes_in_bvh) {
+  int32_t used = 0;
+  return hits_emu_render_opts(desc, cam, node_format, FlattenOptions().tlas_builder, seed, sample_offset, spp, depth, out,
+                              volumes_in_bvh, &used);
+}
+
+// hits_emu_render with the world-BVH builder the caller names (BLAS_REFERENCE
+// / BLAS_SAH); *format_used: the node format the scene took, as
+// hits_emu_run reports it (tests/test_xform_kat.py).
+extern "C" int hits_emu_render_opts(const rt_scene_desc* desc, const rt_camera_desc* cam, int node_format, int tlas_builder,
+                                    uint32_t seed, uint32_t sample_offset, int spp, int depth, float* out,
+                                    int volumes_in_bvh, int32_t* format_used) {
   emu::EmuScene E;
   FlattenOptions fo;
   fo.quant_nodes = node_format;
+  fo.tlas_builder = tlas_builder;
   fo.lift_volumes = volumes_in_bvh ? 0 : 1;
   if (int rc = emu::load_desc(desc, cam, fo, E)) return rc;
   const DScene& sc = E.d;
+  *format_used = sc.wide_nodes ? 2 : sc.quant_nodes ? 1 : 0;
   const bool envis = sc.env.valid && sc.env.use_is && sc.num_lights > 0;   // run_variant
   std::vector<float> frame;
   const int err = wave_run::render(E, seed, sample_offset, uint32_t(spp), uint32_t(spp), depth, envis, frame, nullptr);

@@ -193,6 +193,15 @@ class Builder:
         bb = [pts[:, 0].min(), pts[:, 0].max(), ny.min(), ny.max(), nz.min(), nz.max()]
         return self._add(self.g.RT_ROTATE_X, -1, child, 0, self._pad(bb), [sin_t, cos_t])
 
+    def rotate_z(self, child, sin_t, cos_t):
+        """RotateZ (transform.go:282-319): bbox = the child's corners rotated about z."""
+        b = self.h[child].bbox
+        pts = np.array([[x, y, z] for x in b[0:2] for y in b[2:4] for z in b[4:6]], float)
+        nx = cos_t * pts[:, 0] - sin_t * pts[:, 1]
+        ny = sin_t * pts[:, 0] + cos_t * pts[:, 1]
+        bb = [nx.min(), nx.max(), ny.min(), ny.max(), pts[:, 2].min(), pts[:, 2].max()]
+        return self._add(self.g.RT_ROTATE_Z, -1, child, 0, self._pad(bb), [sin_t, cos_t])
+
     def bvh_node(self, left, right):
         """BVHNode{left, right} (bvh.go): bbox = the union of the children's."""
         l, r = self.h[left].bbox, self.h[right].bbox
