@@ -98,7 +98,9 @@ static void mark_top(OScene* os, int g) {
   if (h->kind == RT_BVH_NODE) {
     mark_top(os, h->a);
     if (h->b != h->a) mark_top(os, h->b);
-  } else if (h->kind == RT_BVH_LEAF) {
+  } else if (h->kind == RT_BVH_LEAF || h->kind == RT_LIST) {
+    /* a list below a world BVH node is a leaf of the world BVH as a BVH leaf is
+       (flatten.cpp tlas_item): its children are the top-level objects */
     for (int i = 0; i < h->b; ++i) os->is_top[os->d->children[h->a + i]] = 1;
   } else {
     os->is_top[g] = 1;

@@ -90,6 +90,7 @@ static int load_desc(const rt_scene_desc* desc, const rt_camera_desc* c, const F
   d.num_planes = int(h.planes.size()); d.num_lights = int(h.lights.size());
   d.num_materials = int(h.materials.size()); d.num_textures = int(h.textures.size());
   d.stack_needed = h.stack_needed;
+  if (h.wide_nodes && h.stack_needed8 > h.stack_needed) d.stack_needed = h.stack_needed8;   // api.cpp upload_one
   d.quant_nodes = h.quant_nodes;
   d.dfs_order = h.dfs_order;
   d.n_nodes = uint32_t(h.nodes4.size()); d.n_leaves = uint32_t(h.leaves.size()); d.n_refs = uint32_t(h.refs.size());

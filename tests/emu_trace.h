@@ -6,6 +6,8 @@
 #include <cstring>
 #include <vector>
 
+#include "../go-raytracing_amd/csrc/wave_layout.h"
+
 namespace emu {
 
 using namespace rtg;
@@ -13,18 +15,22 @@ using namespace rtg;
 constexpr int kTraceRing = 8;
 
 // The buffers k_extend reads and writes for one path slot, and the WaveArgs
-// over them.
+// over them.  The spill area holds what the scene's stack bound leaves beyond
+// the ring (wave_layout.h spill_cap_for, as render_wave and wave_run.h size
+// it), not the kernels' largest depth: a bound one entry short shows here as
+// it would on the device.
 struct TraceArgs {
   std::vector<float4> f4 = std::vector<float4>(size_t(kSlotF4), float4{0.0f, 0.0f, 0.0f, 0.0f});
   std::vector<uint32_t> q = std::vector<uint32_t>(CNT_WORDS_Q, 0u), sj = std::vector<uint32_t>(2, 0u);
   std::vector<uint32_t> pixels = std::vector<uint32_t>(1, 0u);
-  std::vector<uint32_t> spill = std::vector<uint32_t>(size_t(kStackMax - kTraceRing), 0u);
+  std::vector<uint32_t> spill;
   std::vector<double> acc = std::vector<double>(3, 0.0);
   std::vector<unsigned long long> counters = std::vector<unsigned long long>(3 * CNT_BLOCK, 0ull);
   int err = 0;
   WaveArgs a{};
 
-  explicit TraceArgs(int max_depth) {
+  TraceArgs(int max_depth, int stack_needed, int ring = kTraceRing)
+      : spill(size_t(spill_cap_for(stack_needed, ring)), 0u) {
     auto arr = [&](int k) { return &f4[size_t(k)]; };
     for (int k = 0; k < 2; ++k) a.s[k] = PathStream{arr(3 * k), arr(3 * k + 1), arr(3 * k + 2)};
     a.hit = arr(6); a.Lout = arr(7);
@@ -42,7 +48,7 @@ struct TraceArgs {
     a.refill = 1;
     a.spill = spill.data();
     a.spill_lanes = 1;
-    a.spill_cap = kStackMax - kTraceRing;
+    a.spill_cap = int(spill.size());
     a.slots = 1;
     a.out_pixels = 1;
   }
@@ -53,7 +59,7 @@ struct TraceArgs {
 // key: the path's RNG key (d.w of the stream's ray); bounce: the path's
 // bounce as the stream carries it (beta.w bits 16..30), which only the
 // rare-primitive variant (kVol: volumes in the world BVH) reads.
-template <bool kWide, bool kQuant, bool kVol = false>
+template <bool kWide, bool kQuant, bool kVol = false, int kRingN = kTraceRing>
 static float4 trace_variant(const DScene& sc, const DCamera& cam, WaveArgs a, float4 o, float4 d, uint32_t key = 0u,
                             uint32_t bounce = 0u) {
   const uint32_t bw = (bounce & 0x7FFFu) << 16;
@@ -65,10 +71,30 @@ static float4 trace_variant(const DScene& sc, const DCamera& cam, WaveArgs a, fl
   a.s[0].beta[0] = float4{1.0f, 1.0f, 1.0f, bwf};
   a.counts[CNT_STREAM0] = 1u;
   for (uint32_t k = 0; k < kSegs; ++k) a.counts[CNT_FETCH_EXT + k * kSegStride] = 0u;
-  k_extend<kTraceRing, false, kVol, false, kQuant, kWide>(sc, cam, a, a.s[0], a.counts + CNT_STREAM0,
+  k_extend<kRingN, false, kVol, false, kQuant, kWide>(sc, cam, a, a.s[0], a.counts + CNT_STREAM0,
                                                           a.counts + CNT_STREAM1, a.counts + CNT_SHADOW,
                                                           a.counts + CNT_FETCH_SH, a.counts + CNT_FETCH_EXT, 0u);
   return a.hit[0];
+}
+
+// One shadow ray through the production any-hit kernel (wavefront.hip
+// k_shadow, one job: the area-light ray from P along dir to tmax) in the
+// variant of the scene's node format; a.spill_sh is the caller's.  Returns
+// the job's visibility word (bit 0: the ray passed).
+template <bool kWide, bool kQuant, bool kVol = false, int kRingN = kTraceRing>
+static uint32_t shadow_variant(const DScene& sc, WaveArgs a, const float* P, const float* dir, float tmax, uint32_t key,
+                               uint32_t bounce) {
+  float kf;
+  std::memcpy(&kf, &key, 4);
+  a.sj_p[0] = float4{P[0], P[1], P[2], kf};
+  a.sj_a[0] = float4{dir[0], dir[1], dir[2], tmax};
+  a.sj_info[0] = 1u | (bounce << 8);
+  a.sj_vis[0] = 0u;
+  a.counts[cnt_shadow(0)] = 1u;
+  for (uint32_t k = 0; k < kSegs; ++k) a.counts[cnt_fetch_sh(0) + k * kSegStride] = 0u;
+  k_shadow<kRingN, false, kVol, false, kQuant, kWide>(sc, a, a.counts + cnt_shadow(0), a.counts + cnt_fetch_sh(0),
+                                                      a.counts + cnt_fetch_sh(1));
+  return a.sj_vis[0];
 }
 
 // The hit record k_extend stores (store_hit: t, kind << 28 | idx, instance,

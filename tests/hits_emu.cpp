@@ -17,9 +17,12 @@
 // frame (tests/test_path_kat.py), hits_emu_render_opts the same with the
 // world-BVH builder named and the node format taken reported
 // (tests/test_xform_kat.py).  Not a product path.
+#include <algorithm>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <limits>
+#include <string>
 #include <vector>
 
 #include "../go-raytracing_amd/csrc/wavefront.hip"
@@ -66,7 +69,7 @@ extern "C" int hits_emu_run(const rt_scene_desc* desc, const rt_camera_desc* cam
     return 3;
   }
   *format_used = sc.wide_nodes ? 2 : sc.quant_nodes ? 1 : 0;
-  emu::TraceArgs T(E.max_depth);
+  emu::TraceArgs T(E.max_depth, int(E.d.stack_needed));
   for (int i = 0; i < n; ++i) {
     const float4 h = emu::trace_one(E, T, o + 3 * i, d + 3 * i);
     uint32_t w[4];
@@ -145,7 +148,7 @@ extern "C" int hits_emu_run_paths(const rt_scene_desc* desc, const rt_camera_des
   if (int rc = emu::load_desc(desc, cam, fo, E)) return rc;
   const DScene& sc = E.d;
   *format_used = sc.wide_nodes ? 2 : sc.quant_nodes ? 1 : 0;
-  emu::TraceArgs T(E.max_depth);
+  emu::TraceArgs T(E.max_depth, int(E.d.stack_needed));
   for (int i = 0; i < n; ++i) {
     const uint32_t key = path_key(seed, uint32_t(pix[i]), sample);
     const float4 h = emu::trace_path(E, T, o + 3 * i, d + 3 * i, key, uint32_t(bounce));
@@ -244,7 +247,7 @@ extern "C" int hits_emu_shade(const rt_scene_desc* desc, const rt_camera_desc* c
   if (!o && bounce != 0) return 2;
   const DScene& sc = E.d;
   const bool envis = sc.env.valid && sc.env.use_is && sc.num_lights > 0;   // run_variant
-  emu::TraceArgs T(E.max_depth);
+  emu::TraceArgs T(E.max_depth, int(E.d.stack_needed));
   const ShadeOut out{cont, P, sd, nbeta, Ladd, flags, ca, da, tmax_a, ch, dh};
   for (int i = 0; i < n; ++i) {
     const uint32_t key = path_key(seed, uint32_t(pix[i]), sample);
@@ -319,6 +322,206 @@ extern "C" int hits_emu_render_opts(const rt_scene_desc* desc, const rt_camera_d
   const bool envis = sc.env.valid && sc.env.use_is && sc.num_lights > 0;   // run_variant
   std::vector<float> frame;
   const int err = wave_run::render(E, seed, sample_offset, uint32_t(spp), uint32_t(spp), depth, envis, frame, nullptr);
+  memcpy(out, frame.data(), frame.size() * sizeof(float));
+  return err ? 6 : 0;
+}
+
+// ---- the traversal stack bound (tests/test_stack_host.py) -------------------
+namespace {
+
+constexpr int kPeakRing = wave_run::kRing;       // the smallest ring the host pipeline runs with
+constexpr uint32_t kUnwritten = 0xFFFFFFFDu;     // no item (tags end at 13), no entry distance (a NaN), not ITEM_POP / ITEM_NONE
+constexpr int kPeakGuard = 8;
+
+// A spill area of kStackMax words (+ guard words) filled with kUnwritten: what
+// a traversal wrote shows as the highest word that changed.  push spills the
+// ring's oldest entry to word sp - ring when depth sp becomes sp + 1, so the
+// highest word written, k, means the stack held k + ring + 1 words.
+struct PeakArea {
+  std::vector<uint32_t> w = std::vector<uint32_t>(size_t(kStackMax + kPeakGuard), kUnwritten);
+  void reset() { std::fill(w.begin(), w.end(), kUnwritten); }
+  int top() const {
+    int k = int(w.size()) - 1;
+    while (k >= 0 && w[size_t(k)] == kUnwritten) --k;
+    return k;
+  }
+};
+
+template <int R>
+float4 closest_ring(const emu::EmuScene& E, WaveArgs a, const float* o, const float* d, uint32_t key, uint32_t bounce) {
+  const float4 ro{o[0], o[1], o[2], 0.0f}, rd{d[0], d[1], d[2], 0.0f};
+  const DScene& sc = E.d;
+  if (sc.has_volumes != 0 || sc.n_circles > 0 || sc.dfs_order != 0)   // emu::trace_path's rule
+    return sc.quant_nodes ? emu::trace_variant<false, true, true, R>(sc, E.cam, a, ro, rd, key, bounce)
+                          : emu::trace_variant<false, false, true, R>(sc, E.cam, a, ro, rd, key, bounce);
+  return sc.wide_nodes ? emu::trace_variant<true, false, false, R>(sc, E.cam, a, ro, rd, key, bounce)
+         : sc.quant_nodes ? emu::trace_variant<false, true, false, R>(sc, E.cam, a, ro, rd, key, bounce)
+                          : emu::trace_variant<false, false, false, R>(sc, E.cam, a, ro, rd, key, bounce);
+}
+
+template <int R>
+uint32_t anyhit_ring(const emu::EmuScene& E, WaveArgs a, const float* o, const float* d, float tmax, uint32_t key,
+                     uint32_t bounce) {
+  const DScene& sc = E.d;
+  if (sc.has_volumes != 0 || sc.n_circles > 0 || sc.dfs_order != 0)
+    return sc.quant_nodes ? emu::shadow_variant<false, true, true, R>(sc, a, o, d, tmax, key, bounce)
+                          : emu::shadow_variant<false, false, true, R>(sc, a, o, d, tmax, key, bounce);
+  return sc.wide_nodes ? emu::shadow_variant<true, false, false, R>(sc, a, o, d, tmax, key, bounce)
+         : sc.quant_nodes ? emu::shadow_variant<false, true, false, R>(sc, a, o, d, tmax, key, bounce)
+                          : emu::shadow_variant<false, false, false, R>(sc, a, o, d, tmax, key, bounce);
+}
+
+}  // namespace
+
+// What the flattener derives for the traversal stack.  out[0]: flatten_scene's
+// status (the others are then 0); [1] stack_needed, [2] tlas_need4, [3]
+// blas_need4, [4] max_leaf_inst, [5] dfs_order, [6] the node format taken, [7]
+// stack_needed8, [8] tlas_need8, [9] blas_need8 (the 8-wide figures only
+// where that format is taken), [10] BVH4 nodes, [11] 8-wide nodes, [12] BLASes,
+// [13] the bound the kernels' spill area is sized from (api.cpp upload_one).
+// nodes4 (cap4 nodes x 5 words: the four child items, then the mask of used
+// slots), nodes8 (cap8 x 32 words: the records as they are) and roots (the
+// world root item in both forms, then per BLAS its root item in both forms;
+// at most cap_roots words) may be null.
+extern "C" int hits_emu_stack_info(const rt_scene_desc* desc, int tlas_builder, int blas_builder, int node_format, int32_t* out,
+                                   uint32_t* nodes4, int cap4, uint32_t* nodes8, int cap8, uint32_t* roots, int cap_roots) {
+  HostScene h;
+  std::string err;
+  FlattenOptions fo;
+  fo.tlas_builder = tlas_builder;
+  fo.blas_builder = blas_builder;
+  fo.quant_nodes = node_format;
+  for (int i = 0; i < 14; ++i) out[i] = 0;
+  out[0] = flatten_scene(desc, h, err, fo);
+  if (out[0]) { fprintf(stderr, "hits_emu: flatten: %s\n", err.c_str()); return 0; }
+  out[1] = h.stack_needed; out[2] = h.tlas_need4; out[3] = h.blas_need4; out[4] = h.max_leaf_inst; out[5] = h.dfs_order;
+  out[6] = h.wide_nodes ? 2 : h.quant_nodes ? 1 : 0;
+  out[7] = h.stack_needed8; out[8] = h.tlas_need8; out[9] = h.blas_need8;
+  out[10] = int32_t(h.nodes4.size()); out[11] = int32_t(h.nodes8.size()); out[12] = int32_t(h.blas.size());
+  out[13] = h.wide_nodes ? std::max(h.stack_needed, h.stack_needed8) : h.stack_needed;
+  const float inf = std::numeric_limits<float>::infinity();
+  if (nodes4)
+    for (size_t i = 0; i < h.nodes4.size() && i < size_t(cap4); ++i) {
+      uint32_t used = 0;
+      for (int c = 0; c < 4; ++c) {
+        nodes4[5 * i + size_t(c)] = h.nodes4[i].item[c];
+        if (h.nodes4[i].xlo[c] != inf) used |= 1u << c;
+      }
+      nodes4[5 * i + 4] = used;
+    }
+  if (nodes8)
+    for (size_t i = 0; i < h.nodes8.size() && i < size_t(cap8); ++i) memcpy(nodes8 + 32 * i, &h.nodes8[i], 128);
+  if (roots) {
+    std::vector<uint32_t> r{h.tlas.root_item, h.root8};
+    for (size_t b = 0; b < h.blas.size(); ++b) {
+      r.push_back(h.blas[b].root_item);
+      r.push_back(b < h.blas_root8.size() ? h.blas_root8[b] : 0u);
+    }
+    for (size_t i = 0; i < r.size() && i < size_t(cap_roots); ++i) roots[i] = r[i];
+  }
+  return 0;
+}
+
+// n rays through the production kernels with the smallest ring the host
+// pipeline runs with, and each ray's peak stack depth in words, read off the
+// spill area (PeakArea).  any == 0: closest hits (k_extend in the variant
+// launch_wavefront picks, the rare-primitive / reference-order one included;
+// top / prim / t as hits_emu_run_paths); any == 1: shadow rays from o along d
+// to tmax[i] through k_shadow (vis[i]: 1 the ray passed).  tight == 1: the
+// kernels see the product's spill capacity, spill_cap_for(the scene's bound,
+// ring); tight == 0: kStackMax words, so a ray that needs more than the bound
+// shows as a peak above it and not as a dropped entry.  peak[i]: 0 when the
+// ray never left the ring (at most `ring` words), else its deepest stack.
+// info[0] the node format taken, [1] the scene's bound, [2] the ring, [3] the
+// spill capacity given, [4] words written at or past that capacity (never:
+// TStack checks), [5] the kernels' error flag.  Returns 0 or load_desc's code.
+extern "C" int hits_emu_stack_trace(const rt_scene_desc* desc, const rt_camera_desc* cam, int tlas_builder, int blas_builder,
+                                    int node_format, int tight, int any, int bounce, const float* o, const float* d,
+                                    const float* tmax, int n, int32_t* top, int32_t* prim, float* t, int32_t* vis,
+                                    int32_t* peak, int32_t* info) {
+  emu::EmuScene E;
+  FlattenOptions fo;
+  fo.tlas_builder = tlas_builder;
+  fo.blas_builder = blas_builder;
+  fo.quant_nodes = node_format;
+  if (int rc = emu::load_desc(desc, cam, fo, E)) return rc;
+  const DScene& sc = E.d;
+  emu::TraceArgs T(E.max_depth, int(sc.stack_needed), kPeakRing);
+  PeakArea area;
+  const int cap = tight ? spill_cap_for(int(sc.stack_needed), kPeakRing) : kStackMax;
+  T.a.spill = area.w.data();
+  T.a.spill_sh = area.w.data();
+  T.a.spill_cap = cap;
+  int past = 0;
+  for (int i = 0; i < n; ++i) {
+    area.reset();
+    if (any) {
+      vis[i] = int32_t(anyhit_ring<kPeakRing>(E, T.a, o + 3 * i, d + 3 * i, tmax[i], 0u, uint32_t(bounce)) & 1u);
+    } else {
+      const float4 h = closest_ring<kPeakRing>(E, T.a, o + 3 * i, d + 3 * i, 0u, uint32_t(bounce));
+      uint32_t w[4];
+      memcpy(w, &h, 16);
+      top[i] = prim[i] = -1;
+      t[i] = -1.0f;
+      if (w[1] != 0u) {
+        hit_ids(sc, int(w[1] >> 28), int(w[1] & 0x0FFFFFFFu), int(w[3]), top[i], prim[i]);
+        t[i] = h.x;
+      }
+    }
+    const int k = area.top();
+    peak[i] = k < 0 ? 0 : k + kPeakRing + 1;
+    if (k >= cap) ++past;
+  }
+  info[0] = sc.wide_nodes ? 2 : sc.quant_nodes ? 1 : 0;
+  info[1] = int32_t(sc.stack_needed);
+  info[2] = kPeakRing;
+  info[3] = cap;
+  info[4] = past;
+  info[5] = T.err;
+  return 0;
+}
+
+// TStack alone (device_common.h): `n` distinct words pushed onto a stack of
+// `ring` LDS entries (a power of two) over a spill area of spill_cap words,
+// then popped.  popped[i]: the i-th word popped (n of them); *err: the flag
+// push raises; *first_err: the depth at which it was first raised (-1:
+// never); *past: spill words written at or beyond spill_cap.  With n <= ring
+// + spill_cap the words come back in reverse order and the flag stays clear;
+// the push that makes the depth ring + spill_cap + 1 raises it.
+extern "C" int hits_emu_stack_unit(int ring, int spill_cap, int n, uint32_t* popped, int32_t* err, int32_t* first_err,
+                                   int32_t* past) {
+  if (ring <= 0 || (ring & (ring - 1)) != 0 || spill_cap < 0 || spill_cap > kStackMax || n < 0) return 2;
+  std::vector<uint32_t> lds(size_t(ring) + 16, 0u), spill(size_t(kStackMax + kPeakGuard), kUnwritten);
+  const TStack S{lds.data(), 1, ring, spill.data(), lds.data(), 1, spill_cap};
+  int e = 0, sp = 0;
+  *first_err = -1;
+  for (int i = 0; i < n; ++i) {
+    S.push(sp, 0x1000u + uint32_t(i), &e);
+    ++sp;
+    if (e && *first_err < 0) *first_err = sp;
+  }
+  for (int i = 0; i < n; ++i) { --sp; popped[i] = S.pop(sp); }
+  *err = e;
+  *past = 0;
+  for (size_t k = size_t(spill_cap); k < spill.size(); ++k) *past += spill[k] != kUnwritten;
+  return 0;
+}
+
+// hits_emu_render_opts with the mesh builder named too (RT_OPT_BLAS_BUILDER).
+extern "C" int hits_emu_render_blas(const rt_scene_desc* desc, const rt_camera_desc* cam, int node_format, int tlas_builder,
+                                    int blas_builder, uint32_t seed, int spp, int depth, float* out, int32_t* info) {
+  emu::EmuScene E;
+  FlattenOptions fo;
+  fo.quant_nodes = node_format;
+  fo.tlas_builder = tlas_builder;
+  fo.blas_builder = blas_builder;
+  if (int rc = emu::load_desc(desc, cam, fo, E)) return rc;
+  const DScene& sc = E.d;
+  info[0] = sc.wide_nodes ? 2 : sc.quant_nodes ? 1 : 0;
+  info[1] = int32_t(sc.stack_needed);
+  info[2] = spill_cap_for(int(sc.stack_needed), wave_run::kRing);
+  std::vector<float> frame;
+  const int err = wave_run::render(E, seed, 0u, uint32_t(spp), uint32_t(spp), depth, false, frame, nullptr);
   memcpy(out, frame.data(), frame.size() * sizeof(float));
   return err ? 6 : 0;
 }

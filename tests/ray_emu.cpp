@@ -26,7 +26,7 @@ int main(int argc, char** argv) {
     fprintf(stderr, "ray_emu: rare-primitive scenes are not supported\n");
     return 3;
   }
-  emu::TraceArgs T(E.max_depth);
+  emu::TraceArgs T(E.max_depth, int(E.d.stack_needed));
   float o[3], dd[3];
   while (scanf("%f %f %f %f %f %f", &o[0], &o[1], &o[2], &dd[0], &dd[1], &dd[2]) == 6) {
     const float4 h = emu::trace_one(E, T, o, dd);

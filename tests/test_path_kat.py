@@ -47,6 +47,8 @@ order).  Radiance is the sum of the row's samples, absolute error.
                                                       bounce 0's t: 2.39e-5 (object space reaches 32; the ball's normal is
                                                       (P - c) / 0.22 there, times 8 on the way out)
   tree   wrap_inner (3) rot_bvh (2)                 8.58e-7                                  6.08e-6                                  3.07e-7
+  stack  stack_cases: chain_ref chain_dfs inst_leaf    9.46e-7 2.82e-6                          1.93e-5 1.94e-6                          4.43e-6
+         balanced                                     (bounce 1's t: `balanced`, a floor ray that meets a tile after t ~ 0.1)
   A wrapped sphere's feature normal, unit(A^T (P - c) / r) in float32 from the fp32 oracle's t: chain 1.43e-5, stretch 4.40e-3.
 
 The room's relative t error is that large because a scattered ray that
@@ -91,6 +93,8 @@ MEASURED_FP32 = {
     "chain": dict(ray=[1.44e-5, 1.72e-5], t=[1.38e-4, 1.03e-5], L=5.38e-5, t0=3.95e-6, n_ball=1.43e-5),
     "stretch": dict(ray=[4.40e-3, 2.46e-4], t=[1.74e-4, 9.92e-5], L=5.14e-4, t0=2.39e-5, n_ball=4.40e-3),
     "tree": dict(ray=[8.58e-7], t=[6.08e-6], L=3.07e-7),
+    # tests/stack_cases.py (tests/test_stack_host.py)
+    "stack": dict(ray=[9.46e-7, 2.82e-6], t=[1.93e-5, 1.94e-6], L=4.43e-6),
 }
 
 f32p, i32p, u32p = C.POINTER(C.c_float), C.POINTER(C.c_int32), C.POINTER(C.c_uint32)
