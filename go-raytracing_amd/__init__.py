@@ -39,6 +39,8 @@ RT_NODES_FP32, RT_NODES_QUANT8, RT_NODES_WIDE8 = 0, 1, 2
 RT_OPT_DEALING, RT_OPT_DEAL_FIRST = 10, 11
 RT_OPT_TAIL = 12
 RT_OPT_OVERLAP = 13
+RT_OPT_LIFT_PRIMS = 14
+RT_PRIMS_LIFTED, RT_PRIMS_IN_BVH = 0, 1
 RT_DEAL_STATIC, RT_DEAL_DYNAMIC = 0, 1
 STATUS = {0: "RT_OK", -1: "RT_ERR_INVALID", -2: "RT_ERR_UNSUPPORTED", -3: "RT_ERR_HIP", -4: "RT_ERR_OOM",
           -5: "RT_ERR_NO_SCENE", -6: "RT_ERR_DEVICE"}
@@ -201,6 +203,8 @@ def rtgpu() -> C.CDLL:
         lib.rt_scene_upload.argtypes = [P, C.POINTER(RtSceneDesc)]
         lib.rt_scene_get_info.argtypes = [P, C.POINTER(RtSceneInfo)]
         lib.rt_last_build_ms.argtypes = [P, C.POINTER(C.c_double)]
+        if hasattr(lib, "rt_scene_lifted_prims"):   # (an older build under RTGPU_LIB_DIR has none)
+            lib.rt_scene_lifted_prims.argtypes = [P, C.POINTER(I32)]
         lib.rt_render.argtypes = [P, C.POINTER(RtCameraDesc), C.POINTER(RtRenderParams), C.POINTER(C.c_float),
                                   C.POINTER(RtStats)]
         lib.rt_render_device.argtypes = [P, C.POINTER(RtCameraDesc), C.POINTER(RtRenderParams), P, P]
@@ -770,6 +774,17 @@ class Context:
         ms = C.c_double()
         self._check(self._lib.rt_last_build_ms(self._h, C.byref(ms)))
         return ms.value
+
+    def set_lift_prims(self, lifted: bool):
+        """World quads / spheres tested by the shading kernel (default) or inside the traversal
+        (RT_OPT_LIFT_PRIMS); next upload.  Same frames either way."""
+        self.set_option(RT_OPT_LIFT_PRIMS, RT_PRIMS_LIFTED if lifted else RT_PRIMS_IN_BVH)
+
+    def lifted_prims(self) -> int:
+        """World quads / spheres the uploaded scene keeps out of its world BVH (0: none lifted)."""
+        n = C.c_int32()
+        self._check(self._lib.rt_scene_lifted_prims(self._h, C.byref(n)))
+        return n.value
 
     def set_tlas_builder(self, builder: str):
         """World BVH layout: "sah" (default) or "reference"; next upload."""

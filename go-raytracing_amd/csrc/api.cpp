@@ -66,7 +66,8 @@ struct rt_ctx {
   std::vector<hipEvent_t> tev;
   std::vector<uint8_t> tev_class;
   int tev_used = 0;
-  FlattenOptions fopt;
+  // (contexts lift the world quads / spheres, RT_OPT_LIFT_PRIMS; the struct's own default keeps them in the BVH)
+  FlattenOptions fopt = [] { FlattenOptions o; o.lift_prims = 1; return o; }();
   // schedule options (RT_OPT_BATCH_SLOTS / RT_OPT_REFILL / RT_OPT_MAX_BLOCKS /
   // RT_OPT_TAIL / RT_OPT_STREAMS / RT_OPT_OVERLAP; 0 = automatic): they change
   // how the work is dealt, never the result
@@ -496,6 +497,7 @@ int render_wave(rt_ctx* ctx, const DCamera& dc, const rt_render_params* p, const
     a.counters = static_cast<unsigned long long*>(ctx->counters.p);
     a.err = static_cast<int*>(ctx->errflag.p);
     a.refill = knobs.refill;
+    a.nee_probe = run.probing ? 1u : 0u;
     a.spill_lanes = spill.lanes;
     a.spill_cap = spill.cap;
     a.out_pixels = uint32_t(dc.width) * uint32_t(dc.height);
@@ -900,6 +902,11 @@ int rt_ctx_set_option(rt_ctx* ctx, int32_t key, int32_t value) {
     ctx->fopt.lift_volumes = value == RT_VOLUMES_LIFTED ? 1 : 0;
     return RT_OK;
   }
+  if (key == RT_OPT_LIFT_PRIMS) {
+    if (value != RT_PRIMS_LIFTED && value != RT_PRIMS_IN_BVH) return set_err(ctx, RT_ERR_INVALID, "bad lift-prims option");
+    ctx->fopt.lift_prims = value == RT_PRIMS_LIFTED ? 1 : 0;
+    return RT_OK;
+  }
   if (key == RT_OPT_BVH4_COLLAPSE) {
     if (value != RT_COLLAPSE_SAH && value != RT_COLLAPSE_GREEDY) return set_err(ctx, RT_ERR_INVALID, "bad collapse option");
     ctx->fopt.greedy_collapse = value == RT_COLLAPSE_GREEDY ? 1 : 0;
@@ -1138,6 +1145,16 @@ static int upload_one(rt_ctx* ctx, const rt_scene_desc* scene) {
   d.vol_recs = nullptr;
   const std::vector<DVolRec> vrecs = build_vol_recs(h);
   if (!vrecs.empty() && (rc = upload_vec(ctx, vrecs, &d.vol_recs))) { free_scene(ctx); return rc; }
+  // the world quads / spheres lifted out of the world BVH (k_shade's lift variants)
+  d.prim_recs = nullptr;
+  d.num_prim_recs = int32_t(h.prim_recs.size());
+  if (d.num_prim_recs > 0) {
+    if (d.shade_kind != SHADE_LEAN && d.shade_kind != SHADE_MAT) {
+      free_scene(ctx);
+      return set_err(ctx, RT_ERR_INVALID, "internal: lifted primitives in a scene without a lift shading variant");
+    }
+    if ((rc = upload_vec(ctx, h.prim_recs, &d.prim_recs))) { free_scene(ctx); return rc; }
+  }
   build_inst_entries(h);   // BLAS roots are final now
   if ((rc = upload_vec(ctx, h.inst_entries, &d.inst_entry))) { free_scene(ctx); return rc; }
   // every copy and upload kernel has landed before the scene is used (by
@@ -1154,6 +1171,13 @@ static int upload_one(rt_ctx* ctx, const rt_scene_desc* scene) {
 int rt_last_build_ms(const rt_ctx* ctx, double* ms) {
   if (!ctx || !ms) return RT_ERR_INVALID;
   *ms = ctx->build_ms;
+  return RT_OK;
+}
+
+int rt_scene_lifted_prims(const rt_ctx* ctx, int32_t* count) {
+  if (!ctx || !count) return RT_ERR_INVALID;
+  if (!ctx->has_scene) return RT_ERR_NO_SCENE;
+  *count = int32_t(ctx->host.prim_recs.size());
   return RT_OK;
 }
 

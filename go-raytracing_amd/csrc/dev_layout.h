@@ -315,6 +315,27 @@ struct alignas(16) DVolRec {
   DQuad q[kVolRecQuads];
 };
 
+// A world-level quad or sphere lifted out of the world BVH
+// (FlattenOptions::lift_prims): tested by the shading code on every path's ray
+// and NEE shadow ray (lifted_prims, device_common.h) instead of in the
+// traversal.  The record carries what the traversal attached to the
+// primitive: its TLAS ref position (DFS rank, tie rule) and the fp32 box the
+// unlifted traversal tests last before reaching it (its BVH4 slot box, or its
+// reference leaf's box over all the leaf's objects): a primitive is only
+// reached when that box's slab interval is non-empty, and a rim ray can pass
+// the primitive's test and fail the box by an ulp.
+constexpr int kPrimRecMax = 8;    // lifted primitives a scene may have (as kVolRecMax)
+struct alignas(16) DPrimRec {
+  DQuad q;                        // PK_QUAD: the quad, quad_axis_code in pad0
+  DSphere s;                      // PK_SPHERE: the sphere
+  int32_t kind;                   // PK_QUAD / PK_SPHERE
+  int32_t idx;                    // index in DScene.quads / spheres
+  int32_t refpos;                 // TLAS ref position (ref_rank[refpos] = its DFS rank)
+  int32_t has_box;                // 0: the traversal reached it with no box test (a list root)
+  float lo[3], pad0;              // that box
+  float hi[3], pad1;
+};
+
 struct alignas(16) DMaterial {
   int32_t kind;              // rt_material_kind
   int32_t tex;
@@ -376,6 +397,12 @@ struct alignas(16) DRefBox {
 
 // k_shade variants: the material / texture code a scene needs compiled in.
 enum : int32_t { SHADE_LEAN = 0, SHADE_MAT = 1, SHADE_FULL = 2, SHADE_VOL = 3 };
+// Template flag beside the kind (k_shade / k_tail / shade_path): the variant
+// that also tests the lifted world primitives (DScene.prim_recs).  Only the
+// lean and material kinds have one (flatten_scene lifts nothing in scenes that
+// shade with the full or volume variant), so scenes that lift nothing run the
+// code they ran before.
+constexpr int32_t SHADE_LIFT = 8, SHADE_KIND_MASK = 7;
 
 // Everything the kernels need, passed by value as a kernel argument.
 // k_shade copies the material, texture and light tables to LDS (wavefront
@@ -448,6 +475,9 @@ struct DScene {
   // array lengths (bounds checks of the RTG_GUARD diagnostic build)
   uint32_t n_nodes, n_leaves, n_refs, n_spheres, n_quads, n_tris, n_instances, n_blas, n_volumes, n_circles;
   uint32_t n_nodes8, n_litems, n_wtris;
+  // world quads / spheres lifted out of the world BVH (0 / null: none)
+  int32_t num_prim_recs;
+  const DPrimRec* prim_recs;
 };
 
 struct DCamera {

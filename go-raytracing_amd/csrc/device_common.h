@@ -655,6 +655,69 @@ __device__ __forceinline__ void lifted_volumes(const DScene& sc, V3 ro, V3 rd, u
   }
 }
 
+// World quads / spheres lifted out of the world BVH (DPrimRec, FlattenOptions
+// ::lift_prims).  One record against one ray, with trav_step's interval
+// rules for an inline world quad / sphere (kAny: quad t <= tmax, sphere t <
+// tmax; closest hit: the caller's accept rule): the primitive's own test
+// first, and only on a pass the record's box (box_hit over [tmin, tmax], the
+// closest-hit ray's upper bound +inf, which box_hit caps) — the box the
+// unlifted traversal tested last before reaching the primitive, so the
+// decision is the traversal's box-then-primitive at about one box test per
+// ray.  The records are the wave's (scalar loads, as KVolRec).
+typedef const RTG_KAS DPrimRec* KPrimRec;
+__device__ __forceinline__ KPrimRec kprimrec(const DPrimRec* p, int i) { return (KPrimRec)(p) + i; }
+template <bool kAny, bool kCount>
+__device__ __forceinline__ bool prim_rec_t(KPrimRec R, V3 o, V3 d, float time, float tmin, float tmax, float& t,
+                                           Cnt& cnt) {
+  bool ok;
+  if (R->kind == PK_QUAD) {
+    if (kCount) cnt.quad++;
+    const DQuad q = R->q;
+    ok = quad_t_rec(q, o, d, tmin, t) && (kAny ? t <= tmax : true);
+  } else {
+    if (kCount) cnt.sph++;
+    const DSphere s = R->s;
+    ok = sphere_t(s, o, d, time, tmin, t) && (kAny ? t < tmax : true);
+  }
+  if (!ok) return false;
+  if (R->has_box == 0) return true;
+  float tn = 0.0f;
+  return box_hit(R->lo[0], R->hi[0], R->lo[1], R->hi[1], R->lo[2], R->hi[2], make_tray(o, d), tmin,
+                 kAny ? tmax : __builtin_inff(), tn);
+}
+// The closest-hit ray against every lifted primitive, competing with the
+// traversal's hit (kh = kind << 28 | index, 0 = miss; ht; instance; TLAS ref
+// position) by the accept rule: closer, or on an exact tie the reference's
+// DFS order (tie_wins).  shade_path, k_features and the probes call this
+// (and traverse does the same on its Best record).
+template <bool kCount>
+__device__ __forceinline__ void lifted_prims(const DScene& sc, V3 ro, V3 rd, float time, uint32_t& kh, float& ht,
+                                             int& hinst, int& hrefpos, Cnt& cnt) {
+  for (int i = 0; i < sc.num_prim_recs; ++i) {
+    const KPrimRec R = kprimrec(sc.prim_recs, i);
+    float t = 0.0f;
+    if (!prim_rec_t<false, kCount>(R, ro, rd, time, 0.001f, __builtin_inff(), t, cnt)) continue;
+    const int kind = R->kind, refpos = R->refpos;
+    if (kh == 0u || t < ht || (t == ht && tie_wins(sc, kind, refpos, 0, int(kh >> 28), hrefpos, 0))) {
+      kh = (uint32_t(kind) << 28) | uint32_t(R->idx);
+      ht = t;
+      hinst = -1;
+      hrefpos = refpos;
+    }
+  }
+}
+// Is a shadow ray over [0.001, tmax] occluded by a lifted primitive (the
+// any-hit traversal's test of it; k_shadow's rays run at time 0)?
+template <bool kCount>
+__device__ __forceinline__ bool lifted_prims_any(const DScene& sc, V3 o, V3 d, float time, float tmin, float tmax,
+                                                 Cnt& cnt) {
+  for (int i = 0; i < sc.num_prim_recs; ++i) {
+    float t = 0.0f;
+    if (prim_rec_t<true, kCount>(kprimrec(sc.prim_recs, i), o, d, time, tmin, tmax, t, cnt)) return true;
+  }
+  return false;
+}
+
 // ----------------------------------------------------------------------------
 // BVH traversal ("while-while", Aila & Laine 2009, adapted to wave64): one
 // loop for the world BVH and instance BLASes (ray switched to object space on
@@ -1397,7 +1460,17 @@ __device__ bool traverse(const DScene& sc, V3 wo, V3 wd, float time, float tmin,
       best.t = tv; best.kind = PK_VOLUME; best.idx = vr.vol; best.inst = -1; best.refpos = vr.refpos; best.primpos = 0;
     }
   }
-  if (kAny) return false;
+  // world quads / spheres lifted out of the world BVH (DPrimRec): likewise
+  if (kAny) return lifted_prims_any<kCount>(sc, wo, wd, time, tmin, tmax, cnt);
+  for (int i = 0; i < sc.num_prim_recs; ++i) {
+    const KPrimRec R = kprimrec(sc.prim_recs, i);
+    float t = 0.0f;
+    if (!prim_rec_t<false, kCount>(R, wo, wd, time, tmin, __builtin_inff(), t, cnt) || !(t < tmax)) continue;
+    const int kind = R->kind, refpos = R->refpos;
+    if (best.kind == 0 || t < best.t || (t == best.t && tie_wins(sc, kind, refpos, 0, best.kind, best.refpos, best.primpos))) {
+      best.t = t; best.kind = kind; best.idx = R->idx; best.inst = -1; best.refpos = refpos; best.primpos = 0;
+    }
+  }
   return best.kind != 0;
 }
 

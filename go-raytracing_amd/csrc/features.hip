@@ -78,6 +78,7 @@ __global__ __launch_bounds__(256) void k_features(DScene sc, DCamera cam, const 
   int hinst = int(__float_as_uint(h.z)), hrefpos = int(__float_as_uint(h.w));
   Cnt cnt = {};
   if (sc.num_vol_refs > 0) lifted_volumes<false>(sc, ro, rd, key, 0u, kh, ht, hinst, hrefpos, cnt, sc.vol_recs);
+  if (sc.num_prim_recs > 0) lifted_prims<false>(sc, ro, rd, time, kh, ht, hinst, hrefpos, cnt);
   float4 ra = make_float4(0.0f, 0.0f, 0.0f, 0.0f), rb = ra;
   if (kh != 0u) {
     Best b{};

@@ -42,6 +42,8 @@ float round_up(double x) {
   return f;
 }
 
+uint32_t quad_axis_code(const DQuad& q);
+
 namespace {
 
 constexpr double kInf = std::numeric_limits<double>::infinity();
@@ -679,11 +681,73 @@ struct Flattener {
     return true;
   }
 
-  // World leaf: objects in order; planes (and lifted volumes) out, DFS rank kept.
+  // A world quad / sphere lifted out of the world BVH (FlattenOptions::
+  // lift_prims): its ref (DFS rank) outside every world leaf's range, and a
+  // DPrimRec record with the box the unlifted traversal would have tested
+  // last before reaching it.
+  bool lift_p = false;
+  bool lifts(const rt_hittable& h) const { return lift_p && (h.kind == RT_QUAD || h.kind == RT_SPHERE); }
+  bool lift_prim(int g, int rank, const Box& box) {
+    if (!add_object_ref(g, rank)) return false;
+    const uint32_t ref = S.refs.back();
+    DPrimRec r{};
+    r.kind = int32_t(ref >> REF_SHIFT);
+    r.idx = int32_t(ref & REF_MASK);
+    r.refpos = int32_t(S.refs.size() - 1);
+    r.has_box = 1;
+    if (r.kind == PK_QUAD) {
+      r.q = S.quads[size_t(r.idx)];
+      r.q.pad0 = __builtin_bit_cast(float, quad_axis_code(r.q));
+    } else {
+      r.s = S.spheres[size_t(r.idx)];
+    }
+    float b[6];
+    store_box(b, box);
+    for (int a = 0; a < 3; ++a) { r.lo[a] = b[2 * a]; r.hi[a] = b[2 * a + 1]; }
+    S.prim_recs.push_back(r);
+    return true;
+  }
+  // The world's top-level objects by kind (the walk of collect_top /
+  // tlas_item, nothing built): quads and spheres, and every other object a
+  // world leaf would hold (planes never enter the BVH).
+  void count_top(int g, int depth, int& nprim, int& nother) {
+    if (!valid_index(g) || depth > 200) return;
+    const rt_hittable& h = H(g);
+    auto leaf = [&](const std::vector<int>& objs) {
+      for (int o : objs) {
+        if (!valid_index(o)) continue;
+        const int k = H(o).kind;
+        if (k == RT_PLANE) continue;
+        if (k == RT_QUAD || k == RT_SPHERE) nprim++;
+        else nother++;
+      }
+    };
+    if (h.kind == RT_BVH_NODE) {
+      if (!valid_index(h.a) || !valid_index(h.b)) return;
+      if (h.a == h.b) {
+        const rt_hittable& c = H(h.a);
+        if (c.kind == RT_BVH_LEAF) leaf(children_of(c));
+        else if (c.kind != RT_BVH_NODE) leaf({h.a});
+        return;
+      }
+      count_top(h.a, depth + 1, nprim, nother);
+      count_top(h.b, depth + 1, nprim, nother);
+      return;
+    }
+    if (h.kind == RT_BVH_LEAF || h.kind == RT_LIST) leaf(children_of(h));
+    else leaf({g});
+  }
+
+  // World leaf: objects in order; planes (and lifted volumes / primitives) out, DFS rank kept.
   uint32_t tlas_leaf(const std::vector<int>& objs, int ntests, Box& box) {
     std::vector<int> ranks(objs.size());
     for (size_t i = 0; i < objs.size(); ++i) ranks[i] = rank_counter++;
     int count = 0, ninst = 0;
+    // the leaf's box over all its objects, as the unlifted leaf has it: the
+    // box a lifted primitive of this leaf keeps in its record
+    Box full;
+    for (int g : objs)
+      if (lift_p && valid_index(g) && H(g).kind != RT_PLANE) full.merge(H(g).bbox);
     for (size_t i = 0; i < objs.size(); ++i) {
       int g = objs[i];
       const rt_hittable& h = H(g);
@@ -697,7 +761,7 @@ struct Flattener {
         S.plane_hidx.push_back(g);
         continue;
       }
-      if (!(lift && h.kind == RT_VOLUME)) count++;
+      if (!(lift && h.kind == RT_VOLUME) && !lifts(h)) count++;
       // Pre-build BLASes: mixed BLAS leaves append refs, and the refs of
       // this world leaf must stay contiguous.
       int cur = h.kind == RT_VOLUME ? h.a : g;
@@ -711,7 +775,7 @@ struct Flattener {
     for (size_t i = 0; i < objs.size(); ++i) {
       int g = objs[i];
       const rt_hittable& h = H(g);
-      if (h.kind == RT_PLANE || (lift && h.kind == RT_VOLUME)) continue;
+      if (h.kind == RT_PLANE || (lift && h.kind == RT_VOLUME) || lifts(h)) continue;
       if (!add_object_ref(g, ranks[i])) return empty_leaf;
       if ((S.refs.back() >> REF_SHIFT) == uint32_t(PK_INSTANCE)) ninst++;
       box.merge(h.bbox);
@@ -722,6 +786,8 @@ struct Flattener {
     }
     for (size_t i = 0; i < objs.size(); ++i)   // after the leaf's contiguous refs
       if (lift && H(objs[i]).kind == RT_VOLUME && !lift_volume(objs[i], ranks[i], ntests)) return empty_leaf;
+    for (size_t i = 0; i < objs.size(); ++i)
+      if (lifts(H(objs[i])) && !lift_prim(objs[i], ranks[i], full)) return empty_leaf;
     if (count == 0) return empty_leaf;
     if (ninst > 8) { fail(RT_ERR_UNSUPPORTED, "more than 8 instances in one world leaf"); return empty_leaf; }
     if (ninst > max_leaf_inst) max_leaf_inst = ninst;
@@ -903,8 +969,39 @@ struct Flattener {
       }
       top_objs.swap(rest);
     }
+    if (lift_p) {
+      // a lifted primitive's record keeps the box of its own single-object
+      // leaf (sah_top_node: one object per leaf, its bbox the slot box)
+      std::vector<TopObj> rest;
+      for (const TopObj& o : top_objs) {
+        if (!lifts(H(o.g))) { rest.push_back(o); continue; }
+        Box bx;
+        for (int a = 0; a < 3; ++a) { bx.b[2 * a] = o.lo[a]; bx.b[2 * a + 1] = o.hi[a]; }
+        if (!lift_prim(o.g, o.rank, bx)) return empty_leaf;
+      }
+      top_objs.swap(rest);
+    }
     if (top_objs.empty()) return empty_leaf;
     max_leaf_inst = 1;
+    if (lift_p && top_objs.size() == 1) {
+      // One object left beside the lifted primitives: the world keeps a root
+      // node (the object in one slot, the other empty) and not a bare leaf
+      // root, so the world's node count does not depend on whether one or
+      // several objects remain (rt_scene_info.nodes of a scene with one
+      // instance and of the same scene with a second instance of the same
+      // BLAS stay equal, as they are unlifted).
+      const int idx = int(S.nodes.size());
+      S.nodes.push_back(DNode{});
+      Box lb;
+      const uint32_t li = sah_top_node(0, 1, 2, lb);
+      DNode& nd = S.nodes[idx];
+      store_box(nd.l, lb);
+      store_box(nd.r, Box());
+      nd.litem = li;
+      nd.ritem = empty_leaf;
+      root.merge(lb);
+      return (ITEM_NODE << ITEM_SHIFT) | uint32_t(idx);
+    }
     return sah_top_node(0, int(top_objs.size()), 1, root);
   }
 
@@ -1459,6 +1556,14 @@ struct Flattener {
     const int k = dp8_split[n2][1], a = dp8_split[n2][k];
     dp8_frontier(nd.litem, nd.l, a, ch, nc);
     dp8_frontier(nd.ritem, nd.r, k - a, ch, nc);
+    if (lift_p) {
+      // a world leaf whose objects were all lifted out is the empty leaf: it
+      // takes no slot (its empty box would make the node's frame unbounded)
+      int keep = 0;
+      for (int c = 0; c < nc; ++c)
+        if (ch[c].item != empty_leaf) ch[keep++] = ch[c];
+      nc = keep;
+    }
     int slot_of[8];
     assign_slots8(ch, nc, slot_of);
     int at[8];
@@ -1521,7 +1626,7 @@ struct Flattener {
       fill8(ci, ch[at[s]].item & ITEM_MASK, tlas);
       worst = std::max(worst, int(need8[ci]));
     }
-    need8[idx] = (nc - 1) + worst;
+    need8[idx] = std::max(nc - 1, 0) + worst;
   }
   uint32_t build8(uint32_t root2, bool tlas, int& need) {
     need = 0;
@@ -1602,6 +1707,14 @@ struct Flattener {
     for (int i = 0; i < d->num_textures && d->textures; ++i)
       tex = tex || d->textures[i].kind == RT_TEX_NOISE || d->textures[i].kind == RT_TEX_IMAGE;
     lift = opt.lift_volumes && nv > 0 && !circles && !tex;
+    // world quads / spheres out of the world BVH (DPrimRec), all or none
+    if (opt.lift_prims && !lift && !tex && tlas_sah_ok() && d->num_materials <= kLdsMaterials &&
+        d->num_textures <= kLdsTextures) {
+      int nprim = 0, nother = 0;
+      count_top(d->root, 1, nprim, nother);
+      if (status) return status;
+      lift_p = nprim > 0 && nprim <= kPrimRecMax && nother > 0;
+    }
     for (int i = 0; i < d->num_hittables; ++i) {
       const rt_hittable& h = d->hittables[i];
       if ((is_prim(h.kind) || h.kind == RT_PLANE || h.kind == RT_VOLUME) &&
@@ -1637,6 +1750,11 @@ struct Flattener {
     std::vector<uint32_t> blas2;
     for (const DBvh& b : S.blas) blas2.push_back(b.root_item);
     build_bvh4();
+    for (const DPrimRec& r : S.prim_recs)   // (build_bvh4 reset them: no inline world leaf names a lifted one)
+      (r.kind == PK_QUAD ? S.quad_wref : S.sphere_wref)[size_t(r.idx)] = r.refpos;
+    // a list root is walked with no box test (HittableList.Hit)
+    if (!S.tlas.check_box && (ri >> ITEM_SHIFT) != ITEM_NODE)
+      for (DPrimRec& r : S.prim_recs) r.has_box = 0;
     // stack: pending siblings along the worst world path + pending instances
     // in a leaf + the pending item and INST_END marker of an instance entry +
     // pending siblings along the worst BLAS path.
@@ -1781,6 +1899,16 @@ int flatten_scene(const rt_scene_desc* desc, HostScene& out, std::string& err, c
     // BVH, where the traversal's volume variant tests it
     FlattenOptions o = opt;
     o.lift_volumes = 0;
+    out = HostScene{};
+    err.clear();
+    Flattener f(desc, out, err, o);
+    rc = f.run();
+  }
+  if (rc == RT_OK && !out.prim_recs.empty() && big_tables) {
+    // (the light table is only known after the build) such a scene shades in
+    // the full variant, which has no lifted-primitive code
+    FlattenOptions o = opt;
+    o.lift_prims = 0;
     out = HostScene{};
     err.clear();
     Flattener f(desc, out, err, o);

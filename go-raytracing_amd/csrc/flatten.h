@@ -40,6 +40,7 @@ struct HostScene {
   std::vector<DVolume> volumes;
   std::vector<int32_t> volume_hidx;
   std::vector<DVolRef> vol_refs;     // volumes lifted out of the world BVH (FlattenOptions::lift_volumes)
+  std::vector<DPrimRec> prim_recs;   // world quads / spheres lifted out of it (FlattenOptions::lift_prims)
   std::vector<DMaterial> materials;
   std::vector<DTexture> textures;
   std::vector<DLight> lights;
@@ -94,6 +95,13 @@ struct FlattenOptions {
   // so the traversal kernels carry no volume code; only in scenes without
   // circles (the traversal's rare-primitive variant would carry both).
   int lift_volumes = 1;
+  // World-level quads and spheres are kept out of the world BVH and tested
+  // by the shading code (DPrimRec), all or none: when there are at most
+  // kPrimRecMax of them, the scene is not in reference-order mode (RotateX /
+  // RotateZ), another object stays in the world BVH, and the scene shades in
+  // the lean or material variant (no Noise / Image texture, no lifted volume,
+  // tables within LDS).  RT_OPT_LIFT_PRIMS; contexts turn it on.
+  int lift_prims = 0;
   // RT_OPT_BVH4_COLLAPSE: 0 = SAH-optimal BVH2 -> BVH4 collapse, 1 = greedy
   // (open the largest-area internal child); the hits are the same
   int greedy_collapse = 0;

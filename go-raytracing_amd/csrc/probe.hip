@@ -119,6 +119,7 @@ __global__ __launch_bounds__(256) void path_hits_kernel(DScene sc, DCamera cam, 
   int hinst = int(__float_as_uint(h.z)), hrefpos = int(__float_as_uint(h.w));
   Cnt cnt = {};
   if (sc.num_vol_refs > 0) lifted_volumes<false>(sc, ro, rd, key, uint32_t(bounce), kh, ht, hinst, hrefpos, cnt, sc.vol_recs);
+  if (sc.num_prim_recs > 0) lifted_prims<false>(sc, ro, rd, ray_time(key), kh, ht, hinst, hrefpos, cnt);   // as shade_path
   int top = -1, prim = -1;
   if (kh != 0u) hit_ids(sc, int(kh >> 28), int(kh & 0x0FFFFFFFu), hrefpos, top, prim);
   const uint32_t p = pixels[slot % npix];
@@ -139,7 +140,10 @@ __global__ __launch_bounds__(256) void nee_probe_kernel(const uint32_t* sj_info,
   const uint32_t j = blockIdx.x * 256u + threadIdx.x;
   if (j >= npix || j >= *count) return;
   const uint32_t slot = __float_as_uint(ne_a[j].w);
-  out_nee[pixels[slot % npix]] = int32_t((sj_info[j] & 3u) | ((sj_vis[j] & 3u) << 2));
+  // (bits 2 / 3 of sj_info: the ray is occluded by a world primitive lifted out of the BVH that k_shadow
+  // walked, WaveArgs::nee_probe)
+  const uint32_t info = sj_info[j], occ = (info >> 2) & 3u;
+  out_nee[pixels[slot % npix]] = int32_t((info & 3u) | ((sj_vis[j] & 3u & ~occ) << 2));
 }
 
 // Parity probe: first-bounce closest hit of one sample per pixel.

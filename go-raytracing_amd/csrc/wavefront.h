@@ -36,7 +36,7 @@ struct WaveArgs {
   float4* sj_p;     // shadow origin.xyz, RNG path key
   float4* sj_a;     // area-light shadow dir.xyz, tmax
   float4* sj_h;     // HDRI shadow dir.xyz, -
-  uint32_t* sj_info;  // flags (1 area ray, 2 HDRI ray) | bounce << 8
+  uint32_t* sj_info;  // flags (1 area ray, 2 HDRI ray) | bounce << 8 (bits 2 / 3: nee_probe below)
   uint32_t* sj_vis;   // written by k_shadow: bit r set = ray r unoccluded
   float4* ne_a;     // area-light contribution if visible .xyz (without HDRI importance
                     // sampling: already times the throughput), path slot
@@ -51,6 +51,13 @@ struct WaveArgs {
   unsigned long long* counters;
   int* err;
   int32_t refill;   // lanes per wave lacking a prefetched item that trigger a claim
+  // The path probes' renders (rt_shadow_visibility): a shadow ray that a
+  // lifted world primitive occludes stays in its job (traced as the
+  // reference traces it) with bit 2 (area) / 3 (HDRI) of sj_info set, which
+  // the probe reads as "occluded".  0 in every other render: k_shade clears
+  // such a ray and writes no job when none is left.  (In the padding before
+  // `spill`: the struct's size and the other offsets are unchanged.)
+  uint32_t nee_probe;
   uint32_t* spill;  // traversal-stack spill area: spill_cap entries x spill_lanes (k_extend, k_tail)
   uint32_t* spill_sh;   // k_shadow's (its own area when it overlaps the next k_extend: WavePlan::overlap)
   uint32_t spill_lanes;

@@ -336,13 +336,17 @@ __device__ __forceinline__ uint32_t shade_claim(uint32_t* ctr, uint32_t nchunks,
 //   h: the hit record k_extend stores (t, kind << 28 | index, instance, ref)
 //   out: cont (a scattered ray to trace: P, sd, nbeta, nstate), want_shadow
 //   (NEE rays: flags, da / tmax_a / ca, dh / ch)
-template <bool kCount, bool kEnvIS, int kShade, bool kFirst>
+//   kShadeL: the shading kind (SHADE_*), | SHADE_LIFT in the variant that also
+//   tests the world primitives lifted out of the world BVH (DScene.prim_recs)
+template <bool kCount, bool kEnvIS, int kShadeL, bool kFirst>
 __device__ __forceinline__ void shade_path(const DScene& sc, const DCamera& cam, const WaveArgs& a, const DVolRec* vrecs,
                                            const float4 h, const V3 ro, const V3 rd, const V3 beta, const uint32_t key,
                                            const uint32_t slot, const int dleft, const uint32_t bounce, const bool allow,
                                            bool& cont, bool& want_shadow, uint32_t& flags, uint32_t& nstate,
                                            float& tmax_a, V3& P, V3& sd, V3& nbeta, V3& ca, V3& ch, V3& da, V3& dh,
                                            bool& lout_set, Cnt& cnt) {
+  constexpr int kShade = kShadeL & SHADE_KIND_MASK;
+  constexpr bool kLift = (kShadeL & SHADE_LIFT) != 0;
   // L += beta * e on the path's radiance in Lout[slot] (camera.go:466, :481);
   // adding an exact zero (black background) leaves L unchanged, so it is
   // skipped.  At bounce 0 the radiance starts at 0 here (0 + beta * e).
@@ -361,6 +365,10 @@ __device__ __forceinline__ void shade_path(const DScene& sc, const DCamera& cam,
   if (kShade == SHADE_VOL) {
     int hrefpos = int(asu(h.w));
     lifted_volumes<kCount>(sc, ro, rd, key, bounce, kh, ht, hinst, hrefpos, cnt, vrecs);
+  }
+  if (kLift) {
+    int hrefpos = int(asu(h.w));
+    lifted_prims<kCount>(sc, ro, rd, time, kh, ht, hinst, hrefpos, cnt);
   }
 #ifdef RTG_GUARD
   if (kh == 0xFFFFFFFFu) rtg_guard_note(50, slot, bounce);   // hit record never written by k_extend
@@ -514,6 +522,16 @@ __device__ __forceinline__ void shade_path(const DScene& sc, const DCamera& cam,
               flags &= ~1u;
           }
         }
+        if (kLift && flags != 0u) {
+          // a lifted world quad / sphere occluding a shadow ray (k_shadow's
+          // any-hit test of it, same intervals; shadow rays run at time 0)
+          // clears the ray; a job with no ray left is not written
+          uint32_t occ = 0u;
+          if ((flags & 2u) && lifted_prims_any<kCount>(sc, P, dh, 0.0f, 0.001f, __builtin_inff(), cnt)) occ |= 2u;
+          if ((flags & 1u) && lifted_prims_any<kCount>(sc, P, da, 0.0f, 0.001f, tmax_a, cnt)) occ |= 1u;
+          // (the path probes keep the ray and mark it, WaveArgs::nee_probe)
+          flags = a.nee_probe ? (flags | (occ << 2)) : (flags & ~occ);
+        }
         want_shadow = flags != 0u;
       }
       nbeta = mul(beta, att);
@@ -571,13 +589,14 @@ __device__ __forceinline__ void shade_tables_to_lds(DScene& sc, char* s_dyn) {
 //     16 / 53 spilled).
 // A separate occupancy for bounce 0's variants (6 / 5 waves) was no faster.
 constexpr int kShadeFullWaves = 4, kShadeLeanWaves = 7, kShadeMatWaves = 7, kShadeVolWaves = 6;
-#define SHADE_WAVES(kShade)                                                     \
-  ((kShade) == SHADE_FULL ? kShadeFullWaves : (kShade) == SHADE_MAT ? kShadeMatWaves \
-   : (kShade) == SHADE_VOL ? kShadeVolWaves : kShadeLeanWaves)
+#define SHADE_WAVES(kShadeL)                                                    \
+  (((kShadeL) & SHADE_KIND_MASK) == SHADE_FULL ? kShadeFullWaves                 \
+   : ((kShadeL) & SHADE_KIND_MASK) == SHADE_MAT ? kShadeMatWaves                 \
+   : ((kShadeL) & SHADE_KIND_MASK) == SHADE_VOL ? kShadeVolWaves : kShadeLeanWaves)
 // kFirst: bounce 0 — the path is the slot's camera ray (no stream to read)
 // and this kernel initialises the slot's radiance in Lout.
-template <bool kCount, bool kEnvIS, int kShade, bool kFirst>
-static __global__ __launch_bounds__(256, SHADE_WAVES(kShade)) void k_shade(DScene scg, DCamera cam, WaveArgs a, PathStream cs,
+template <bool kCount, bool kEnvIS, int kShadeL, bool kFirst>
+static __global__ __launch_bounds__(256, SHADE_WAVES(kShadeL)) void k_shade(DScene scg, DCamera cam, WaveArgs a, PathStream cs,
                                                const uint32_t* count, PathStream ns, uint32_t* ncount,
                                                uint32_t* jcount, uint32_t sample_base, uint32_t launch_bounce) {
   // Small scene tables (materials, textures, lights) are read from LDS: they
@@ -590,6 +609,7 @@ static __global__ __launch_bounds__(256, SHADE_WAVES(kShade)) void k_shade(DScen
 #endif
   __shared__ uint32_t s_w[2][2][4];
   __shared__ uint32_t s_b[2][2];
+  constexpr int kShade = kShadeL & SHADE_KIND_MASK;
   DScene sc = scg;
   // the lifted volumes' records (SHADE_VOL), read from global memory: their
   // addresses are uniform over the wave, so these are scalar loads (a copy in
@@ -667,7 +687,7 @@ static __global__ __launch_bounds__(256, SHADE_WAVES(kShade)) void k_shade(DScen
         rd = mk(d4.x, d4.y, d4.z);
         beta = mk(b4.x, b4.y, b4.z);
       }
-      shade_path<kCount, kEnvIS, kShade, kFirst>(sc, cam, a, vrecs, h, ro, rd, beta, key, slot, dleft, bounce, allow, cont,
+      shade_path<kCount, kEnvIS, kShadeL, kFirst>(sc, cam, a, vrecs, h, ro, rd, beta, key, slot, dleft, bounce, allow, cont,
                                                  want_shadow, flags, nstate, tmax_a, P, sd, nbeta, ca, ch, da, dh,
                                                  lout_set, cnt);
     }
@@ -716,7 +736,7 @@ static __global__ __launch_bounds__(256, SHADE_WAVES(kShade)) void k_shade(DScen
 // the same Lout[slot] adds), so the frame is bit-identical.  Scenes with
 // lights keep the wavefront schedule: their NEE jobs need k_shadow.
 constexpr int kTailWaves = 4;
-template <int STACK, bool kVol, int kShade, bool kQuant, bool kWide>
+template <int STACK, bool kVol, int kShadeL, bool kQuant, bool kWide>
 static __global__ __launch_bounds__(256, kTailWaves) void k_tail(DScene scg, DCamera cam, WaveArgs a, PathStream cs,
                                                               const uint32_t* count, uint32_t* fetch) {
   __shared__ uint32_t lds_stack[(STACK + kWorldRayWords + kWorldInvWords + kHitWords) * 256];   // stack ring + world ray + hit record
@@ -727,6 +747,7 @@ static __global__ __launch_bounds__(256, kTailWaves) void k_tail(DScene scg, DCa
 #else
   extern __shared__ char s_dyn[];   // shade_lds_bytes(sc), as k_shade
 #endif
+  constexpr int kShade = kShadeL & SHADE_KIND_MASK;
   DScene sc = scg;
   lds_nodes_fill<kLds>(sc, lds_nodes);
   if (kShade != SHADE_FULL || shade_tables_fit(sc)) shade_tables_to_lds(sc, s_dyn);   // k_shade's LDS tables
@@ -777,7 +798,7 @@ static __global__ __launch_bounds__(256, kTailWaves) void k_tail(DScene scg, DCa
       uint32_t flags = 0, nstate = 0;
       float tmax_a = 0.0f;
       V3 P = mk(0.0f, 0.0f, 0.0f), sd = P, nbeta = P, ca = P, ch = P, da = P, dh = P;
-      shade_path<false, false, kShade, false>(sc, cam, a, sc.vol_recs, h, ro, rd, beta, key, slot, int(st & 0xFFFFu),
+      shade_path<false, false, kShadeL, false>(sc, cam, a, sc.vol_recs, h, ro, rd, beta, key, slot, int(st & 0xFFFFu),
                                               (st >> 16) & 0x7FFFu, (st >> 31) != 0u, cont, want_shadow, flags, nstate,
                                               tmax_a, P, sd, nbeta, ca, ch, da, dh, lout_set, cnt);
       if (cont) {   // the next bounce of the same path (k_shade's survivor record)
@@ -1223,12 +1244,16 @@ static hipError_t run_variant(const DScene& sc, const DCamera& cam, const WaveAr
   // (sampleLightMIS needs one, camera.go:502): without lights the kEnvIS code
   // is dead, and its registers spilled (C5: 34 VGPRs in bounce 0's shading)
   const bool envis = sc.env.valid && sc.env.use_is && sc.num_lights > 0;
-  const int shade = sc.shade_kind;
+  const int shade = sc.shade_kind | (sc.num_prim_recs > 0 ? SHADE_LIFT : 0);
   auto by_shade = [&](auto E, auto Q, auto W) {
     constexpr bool kE = decltype(E)::value, kQ = decltype(Q)::value, kW = decltype(W)::value;
     if (shade == SHADE_FULL) return run_batches<S, C, V, kE, SHADE_FULL, kQ, kW>(sc, cam, as, sts, plan);
     if (shade == SHADE_VOL) return run_batches<S, C, V, kE, SHADE_VOL, kQ, kW>(sc, cam, as, sts, plan);
     if (shade == SHADE_MAT) return run_batches<S, C, V, kE, SHADE_MAT, kQ, kW>(sc, cam, as, sts, plan);
+    // the variants that test the lifted world primitives (lean / material
+    // scenes only, flatten_scene)
+    if (shade == (SHADE_MAT | SHADE_LIFT)) return run_batches<S, C, V, kE, SHADE_MAT | SHADE_LIFT, kQ, kW>(sc, cam, as, sts, plan);
+    if (shade == (SHADE_LEAN | SHADE_LIFT)) return run_batches<S, C, V, kE, SHADE_LEAN | SHADE_LIFT, kQ, kW>(sc, cam, as, sts, plan);
     return run_batches<S, C, V, kE, SHADE_LEAN, kQ, kW>(sc, cam, as, sts, plan);
   };
   auto by_env = [&](auto Q, auto W) {

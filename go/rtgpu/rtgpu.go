@@ -109,6 +109,9 @@ const (
 	OptDealFirst    int32 = 11 // RT_OPT_DEAL_FIRST
 	OptTail         int32 = 12 // RT_OPT_TAIL
 	OptOverlap      int32 = 13 // RT_OPT_OVERLAP
+	OptLiftPrims    int32 = 14 // RT_OPT_LIFT_PRIMS
+	PrimsLifted     int32 = 0  // RT_PRIMS_LIFTED
+	PrimsInBVH      int32 = 1  // RT_PRIMS_IN_BVH
 	DealStatic      int32 = 0  // RT_DEAL_STATIC
 	DealDynamic     int32 = 1  // RT_DEAL_DYNAMIC
 )
@@ -460,6 +463,14 @@ func (c *Ctx) Info() (SceneInfo, error) {
 	var info SceneInfo
 	err := c.check(C.rt_scene_get_info(c.p, (*C.rt_scene_info)(unsafe.Pointer(&info))))
 	return info, err
+}
+
+// LiftedPrims returns how many world quads / spheres the uploaded scene keeps
+// out of its world BVH (rt_scene_lifted_prims, OptLiftPrims; 0: none lifted).
+func (c *Ctx) LiftedPrims() (int, error) {
+	var n C.int32_t
+	err := c.check(C.rt_scene_lifted_prims(c.p, &n))
+	return int(n), err
 }
 
 // RenderParams is one rt_render call: samplesForPass / depthForPass of

@@ -336,6 +336,26 @@ int rt_last_dealing(const rt_ctx* ctx, int32_t* tiles, int32_t* runs, int32_t ma
  *     ray's whole interval and competes by the tie rule); RT_VOLUMES_IN_BVH
  *     = tested inside the traversal.  Scenes with a Circle or a Noise /
  *     Image texture always keep them in the BVH.
+ *   RT_OPT_LIFT_PRIMS: RT_PRIMS_LIFTED (default) = the world-level quads
+ *     and spheres (room walls, lights: top-level objects, not those inside
+ *     an instance) are kept out of the world BVH and tested by the shading
+ *     kernel on every path ray and NEE shadow ray, so rays that enter no
+ *     instance leave the traversal kernels at once.  Same results: each
+ *     test is confirmed by the fp32 box the traversal would have tested
+ *     before it and competes by the tie rule.  (With RT_NODES_QUANT8 /
+ *     RT_NODES_WIDE8 the traversal tests a slightly wider box than that
+ *     one, so a ray within a few ulps of a primitive's rim can hit it
+ *     inside the traversal and miss it lifted, where it decides as with
+ *     RT_NODES_FP32 and as the reference; frames of the two placements are
+ *     equal with fp32 nodes, and with the quantised formats unless such a
+ *     ray occurs.)  All or none are lifted, only when every one of these
+ *     holds: there are at most 8; the scene holds no RotateX / RotateZ;
+ *     another object (an instance, say) stays in the world BVH; the scene
+ *     has no Noise / Image texture and no lifted volume; and its material,
+ *     texture and light tables have at most 384 / 384 / 16 entries (the
+ *     shading kernel's tables in LDS).  Otherwise, and with
+ *     RT_PRIMS_IN_BVH, the traversal tests them.  rt_scene_lifted_prims
+ *     reports how many the uploaded scene lifted.
  *   RT_OPT_BVH4_COLLAPSE: how the binary BVHs become the 4-wide nodes the
  *     device traverses: RT_COLLAPSE_SAH (default) = the cut of each subtree
  *     into at most four child items with the least total node surface area
@@ -390,7 +410,8 @@ int rt_last_dealing(const rt_ctx* ctx, int32_t* tiles, int32_t* runs, int32_t ma
 enum { RT_OPT_BLAS_BUILDER = 1, RT_OPT_TLAS_BUILDER = 2, RT_OPT_NODE_FORMAT = 3,
        RT_OPT_BATCH_SLOTS = 4, RT_OPT_REFILL = 5, RT_OPT_MAX_BLOCKS = 6, RT_OPT_STREAMS = 7,
        RT_OPT_VOLUMES = 8, RT_OPT_BVH4_COLLAPSE = 9, RT_OPT_DEALING = 10, RT_OPT_DEAL_FIRST = 11,
-       RT_OPT_TAIL = 12, RT_OPT_OVERLAP = 13 };
+       RT_OPT_TAIL = 12, RT_OPT_OVERLAP = 13, RT_OPT_LIFT_PRIMS = 14 };
+enum { RT_PRIMS_LIFTED = 0, RT_PRIMS_IN_BVH = 1 };
 enum { RT_DEAL_STATIC = 0, RT_DEAL_DYNAMIC = 1 };
 enum { RT_BLAS_REFERENCE = 0, RT_BLAS_SAH = 1, RT_BLAS_DEVICE = 2 };
 enum { RT_NODES_FP32 = 0, RT_NODES_QUANT8 = 1, RT_NODES_WIDE8 = 2 };
@@ -402,6 +423,10 @@ int rt_ctx_set_option(rt_ctx* ctx, int32_t key, int32_t value);
 int rt_scene_upload(rt_ctx* ctx, const rt_scene_desc* scene);
 
 int rt_scene_get_info(const rt_ctx* ctx, rt_scene_info* out);
+
+/* World quads / spheres the uploaded scene keeps out of its world BVH
+ * (RT_OPT_LIFT_PRIMS; 0 = none lifted). */
+int rt_scene_lifted_prims(const rt_ctx* ctx, int32_t* count);
 
 /* Wall time (ms) of the device BVH builds (RT_BLAS_DEVICE) of the last
  * rt_scene_upload on this context; 0 when every BLAS was built on the host. */
