@@ -1077,49 +1077,8 @@ static int upload_one(rt_ctx* ctx, const rt_scene_desc* scene) {
     UP(wtris, wtris);
   }
 #undef UP
-  d.tlas = h.tlas;
-  d.env.valid = h.env_valid;
-  d.env.width = h.env_w;
-  d.env.height = h.env_h;
-  d.env.use_is = h.env_use_is;
-  d.env.rotation = h.env_rotation;
-  d.env.total_power = h.env_total_power;
-  d.num_planes = int(h.planes.size());
-  d.num_lights = int(h.lights.size());
-  d.num_materials = int(h.materials.size());
-  d.num_textures = int(h.textures.size());
-  d.stack_needed = h.stack_needed;
-  d.quant_nodes = h.quant_nodes;
-  d.dfs_order = h.dfs_order;
-  d.wide_nodes = h.wide_nodes;
-  d.root8 = h.root8;
-  if (h.wide_nodes) d.stack_needed = std::max(h.stack_needed, h.stack_needed8);
-  d.n_nodes = uint32_t(h.nodes4.size()); d.n_leaves = uint32_t(h.leaves.size()); d.n_refs = uint32_t(h.refs.size());
-  d.n_spheres = uint32_t(h.spheres.size()); d.n_quads = uint32_t(h.quads.size()); d.n_tris = uint32_t(h.tris.size());
-  d.n_instances = uint32_t(h.instances.size()); d.n_blas = uint32_t(h.blas.size());
-  d.n_volumes = uint32_t(h.volumes.size());
-  d.n_circles = uint32_t(h.circles.size());
-  d.n_nodes8 = uint32_t(h.nodes8.size()); d.n_litems = uint32_t(h.litems.size()); d.n_wtris = uint32_t(h.wtris.size());
-  d.shade_kind = SHADE_LEAN;   // the k_shade variant (wavefront.hip)
-  for (const DMaterial& m : h.materials)
-    if (m.kind == RT_METAL || m.kind == RT_DIELECTRIC || m.kind == RT_ISOTROPIC) d.shade_kind = SHADE_MAT;
-  d.needs_uv = 0;
-  for (const DTexture& t : h.textures) {
-    if (t.kind == RT_TEX_IMAGE) d.needs_uv = 1;
-    if (t.kind == RT_TEX_IMAGE || t.kind == RT_TEX_NOISE) d.shade_kind = SHADE_FULL;   // the full tex_value / make_record
-  }
-  // volumes lifted out of the world BVH (flatten: no circles, no Noise /
-  // Image textures) are tested in k_shade's volume variant
-  d.num_vol_refs = int32_t(h.vol_refs.size());
-  d.has_volumes = h.volumes.size() > h.vol_refs.size() ? 1 : 0;
-  if (d.num_vol_refs > 0) d.shade_kind = SHADE_VOL;
-  // the lean / material / volume shading variants read the tables from LDS
-  // only (flatten_scene lifts no volume when they do not fit)
-  if (h.materials.size() > size_t(kLdsMaterials) || h.textures.size() > size_t(kLdsTextures) ||
-      h.lights.size() > size_t(kLdsLights)) {
-    if (d.shade_kind == SHADE_VOL) { free_scene(ctx); return set_err(ctx, RT_ERR_INVALID, "internal: lifted volumes with tables beyond LDS"); }
-    d.shade_kind = SHADE_FULL;
-  }
+  // every scalar of the scene (counts, node format, shading variant): flatten.h
+  if ((rc = scene_scalars(h, d, err))) { free_scene(ctx); return set_err(ctx, rc, err); }
   ctx->dev_nodes = ctx->dev_leaves = 0;
   ctx->build_ms = 0.0;
   if (!h.device_builds.empty() && (rc = device_builds(ctx))) { free_scene(ctx); return rc; }
@@ -1142,19 +1101,10 @@ static int upload_one(rt_ctx* ctx, const rt_scene_desc* scene) {
     return rc;
   }
   // the lifted volumes as DVolRec records (k_shade keeps them in LDS)
-  d.vol_recs = nullptr;
   const std::vector<DVolRec> vrecs = build_vol_recs(h);
   if (!vrecs.empty() && (rc = upload_vec(ctx, vrecs, &d.vol_recs))) { free_scene(ctx); return rc; }
   // the world quads / spheres lifted out of the world BVH (k_shade's lift variants)
-  d.prim_recs = nullptr;
-  d.num_prim_recs = int32_t(h.prim_recs.size());
-  if (d.num_prim_recs > 0) {
-    if (d.shade_kind != SHADE_LEAN && d.shade_kind != SHADE_MAT) {
-      free_scene(ctx);
-      return set_err(ctx, RT_ERR_INVALID, "internal: lifted primitives in a scene without a lift shading variant");
-    }
-    if ((rc = upload_vec(ctx, h.prim_recs, &d.prim_recs))) { free_scene(ctx); return rc; }
-  }
+  if (d.num_prim_recs > 0 && (rc = upload_vec(ctx, h.prim_recs, &d.prim_recs))) { free_scene(ctx); return rc; }
   build_inst_entries(h);   // BLAS roots are final now
   if ((rc = upload_vec(ctx, h.inst_entries, &d.inst_entry))) { free_scene(ctx); return rc; }
   // every copy and upload kernel has landed before the scene is used (by

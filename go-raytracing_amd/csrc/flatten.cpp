@@ -1882,6 +1882,59 @@ std::vector<DVolRec> build_vol_recs(const HostScene& h) {
   return recs;
 }
 
+int scene_scalars(const HostScene& h, DScene& d, std::string& err) {
+  d.tlas = h.tlas;
+  d.env.valid = h.env_valid;
+  d.env.width = h.env_w;
+  d.env.height = h.env_h;
+  d.env.use_is = h.env_use_is;
+  d.env.rotation = h.env_rotation;
+  d.env.total_power = h.env_total_power;
+  d.num_planes = int(h.planes.size());
+  d.num_lights = int(h.lights.size());
+  d.num_materials = int(h.materials.size());
+  d.num_textures = int(h.textures.size());
+  d.stack_needed = h.stack_needed;
+  d.quant_nodes = h.quant_nodes;
+  d.dfs_order = h.dfs_order;
+  d.wide_nodes = h.wide_nodes;
+  d.root8 = h.root8;
+  if (h.wide_nodes) d.stack_needed = std::max(h.stack_needed, h.stack_needed8);
+  d.n_nodes = uint32_t(h.nodes4.size()); d.n_leaves = uint32_t(h.leaves.size()); d.n_refs = uint32_t(h.refs.size());
+  d.n_spheres = uint32_t(h.spheres.size()); d.n_quads = uint32_t(h.quads.size()); d.n_tris = uint32_t(h.tris.size());
+  d.n_instances = uint32_t(h.instances.size()); d.n_blas = uint32_t(h.blas.size());
+  d.n_volumes = uint32_t(h.volumes.size());
+  d.n_circles = uint32_t(h.circles.size());
+  d.n_nodes8 = uint32_t(h.nodes8.size()); d.n_litems = uint32_t(h.litems.size()); d.n_wtris = uint32_t(h.wtris.size());
+  d.shade_kind = SHADE_LEAN;   // the k_shade variant (wavefront.hip)
+  for (const DMaterial& m : h.materials)
+    if (m.kind == RT_METAL || m.kind == RT_DIELECTRIC || m.kind == RT_ISOTROPIC) d.shade_kind = SHADE_MAT;
+  d.needs_uv = 0;
+  for (const DTexture& t : h.textures) {
+    if (t.kind == RT_TEX_IMAGE) d.needs_uv = 1;
+    if (t.kind == RT_TEX_IMAGE || t.kind == RT_TEX_NOISE) d.shade_kind = SHADE_FULL;   // the full tex_value / make_record
+  }
+  // volumes lifted out of the world BVH (flatten: no circles, no Noise /
+  // Image textures) are tested in k_shade's volume variant
+  d.num_vol_refs = int32_t(h.vol_refs.size());
+  d.has_volumes = h.volumes.size() > h.vol_refs.size() ? 1 : 0;
+  if (d.num_vol_refs > 0) d.shade_kind = SHADE_VOL;
+  // the lean / material / volume shading variants read the tables from LDS
+  // only (flatten_scene lifts no volume when they do not fit)
+  if (h.materials.size() > size_t(kLdsMaterials) || h.textures.size() > size_t(kLdsTextures) ||
+      h.lights.size() > size_t(kLdsLights)) {
+    if (d.shade_kind == SHADE_VOL) { err = "internal: lifted volumes with tables beyond LDS"; return RT_ERR_INVALID; }
+    d.shade_kind = SHADE_FULL;
+  }
+  // the world quads / spheres lifted out of the world BVH (k_shade's lift variants)
+  d.num_prim_recs = int32_t(h.prim_recs.size());
+  if (d.num_prim_recs > 0 && d.shade_kind != SHADE_LEAN && d.shade_kind != SHADE_MAT) {
+    err = "internal: lifted primitives in a scene without a lift shading variant";
+    return RT_ERR_INVALID;
+  }
+  return RT_OK;
+}
+
 int flatten_scene(const rt_scene_desc* desc, HostScene& out, std::string& err, const FlattenOptions& opt) {
   out = HostScene{};
   int rc;

@@ -117,6 +117,14 @@ void build_inst_entries(HostScene& S);
 // kVolRecMax of them; else empty.  Call once the BLAS roots are final.
 std::vector<DVolRec> build_vol_recs(const HostScene& S);
 
+// Every non-pointer field of DScene that follows from the flattened scene
+// (header, environment, counts, node format, stack bound, shading variant):
+// the one derivation, for rt_scene_upload and the kernels' host emulations.
+// Returns RT_OK, or RT_ERR_INVALID with `err` set for the two internal errors
+// (lifted volumes with tables beyond LDS; lifted primitives without a lift
+// shading variant).
+int scene_scalars(const HostScene& h, DScene& d, std::string& err);
+
 // Returns RT_OK or an rt_status; `err` receives a message.
 int flatten_scene(const rt_scene_desc* desc, HostScene& out, std::string& err,
                   const FlattenOptions& opt = FlattenOptions());

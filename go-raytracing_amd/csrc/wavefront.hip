@@ -25,6 +25,7 @@
 
 #include "dev_layout.h"
 #include "device_common.h"
+#include "wave_variant.h"
 #include "wavefront.h"
 
 namespace rtg {
@@ -1033,6 +1034,31 @@ static hipError_t mark_end(const WavePlan& plan, hipStream_t st) {
     }                                                                                                  \
   } while (0)
 
+// One variant's kernels, as typed pointers to the __global__ functions: all
+// that the variant's template parameters decide about the schedule below.
+using ExtendFn = void (*)(DScene, DCamera, WaveArgs, PathStream, const uint32_t*, uint32_t*, uint32_t*, uint32_t*, uint32_t*,
+                          uint32_t);
+using ShadeFn = void (*)(DScene, DCamera, WaveArgs, PathStream, const uint32_t*, PathStream, uint32_t*, uint32_t*, uint32_t,
+                         uint32_t);
+using ShadowFn = void (*)(DScene, WaveArgs, const uint32_t*, uint32_t*, uint32_t*);
+using NeeApplyFn = void (*)(WaveArgs, const uint32_t*);
+using TailFn = void (*)(DScene, DCamera, WaveArgs, PathStream, const uint32_t*, uint32_t*);
+struct WaveKernels {
+  ExtendFn extend0, extend;   // bounce 0 (camera rays), later bounces
+  ShadeFn shade0, shade;
+  ShadowFn shadow;
+  NeeApplyFn nee_apply;
+  TailFn tail;                // null in the counting variants: they hand nothing to k_tail
+  bool count;
+};
+template <int STACK, bool C, bool V, bool E, int S, bool Q, bool W>
+static WaveKernels kernels_for() {
+  TailFn tail = nullptr;
+  if constexpr (!C) tail = k_tail<STACK, V, S, Q, W>;
+  return {k_extend<STACK, C, V, true, Q, W>, k_extend<STACK, C, V, false, Q, W>, k_shade<C, E, S, true>,
+          k_shade<C, E, S, false>, k_shadow<STACK, C, V, E, Q, W>, k_nee_apply<E>, tail, C};
+}
+
 // The render's work is split into twins (WavePlan::num_twins, 1 or 2):
 // disjoint halves of the pixel list, each with its own path slots, queue
 // counters, spill area and HIP stream, enqueued bounce by bounce in
@@ -1043,9 +1069,8 @@ static hipError_t mark_end(const WavePlan& plan, hipStream_t st) {
 // compute units those waves free, so the tails overlap with work.  Each
 // pixel belongs to one twin and keeps its sample order: the frame is
 // bit-identical to a one-stream render.
-template <int STACK, bool kCount, bool kVol, bool kEnvIS, int kShade, bool kQuant, bool kWide>
-static hipError_t run_batches(const DScene& sc, const DCamera& cam, const WaveArgs* as, const hipStream_t* sts,
-                              const WavePlan& plan) {
+static hipError_t run_batches(const WaveKernels& k, const DScene& sc, const DCamera& cam, const WaveArgs* as,
+                              const hipStream_t* sts, const WavePlan& plan) {
   const int cus = plan.num_cus;
   const int nt = plan.num_twins;
   const bool nee = sc.num_lights > 0;
@@ -1060,16 +1085,16 @@ static hipError_t run_batches(const DScene& sc, const DCamera& cam, const WaveAr
       const hipStream_t st = sts[t];
       const uint32_t nslots = sb * a.npix;
       hipLaunchKernelGGL(k_set_counts, dim3(1), dim3(1), 0, st, a.counts, nslots);
-      if (kCount) hipLaunchKernelGGL(k_count_samples, dim3(1), dim3(1), 0, st, a, nslots);
+      if (k.count) hipLaunchKernelGGL(k_count_samples, dim3(1), dim3(1), 0, st, a, nslots);
       // one spill column per resident lane; RT_OPT_MAX_BLOCKS may cap it further
       int max_trav_blocks = int(a.spill_lanes / 256u);
       if (plan.max_blocks > 0 && plan.max_blocks < max_trav_blocks) max_trav_blocks = plan.max_blocks;
       auto cap = [&](int g) { return g < max_trav_blocks ? g : max_trav_blocks; };
-      gsh[t] = grid_for((const void*)k_shade<kCount, kEnvIS, kShade, false>, 256, shade_lds, nslots, cus);
-      gsd[t] = cap(grid_for((const void*)k_shadow<STACK, kCount, kVol, kEnvIS, kQuant, kWide>, 256, 0, nslots, cus));
-      gap[t] = grid_for((const void*)k_nee_apply<kEnvIS>, 256, 0, nslots, cus);
-      gext0[t] = cap(grid_for((const void*)k_extend<STACK, kCount, kVol, true, kQuant, kWide>, 256, 0, nslots, cus));
-      gext[t] = cap(grid_for((const void*)k_extend<STACK, kCount, kVol, false, kQuant, kWide>, 256, 0, nslots, cus));
+      gsh[t] = grid_for((const void*)k.shade, 256, shade_lds, nslots, cus);
+      gsd[t] = cap(grid_for((const void*)k.shadow, 256, 0, nslots, cus));
+      gap[t] = grid_for((const void*)k.nee_apply, 256, 0, nslots, cus);
+      gext0[t] = cap(grid_for((const void*)k.extend0, 256, 0, nslots, cus));
+      gext[t] = cap(grid_for((const void*)k.extend, 256, 0, nslots, cus));
     }
     if (plan.bounces_run) *plan.bounces_run = 0;
     if (plan.feat_acc) {
@@ -1080,7 +1105,7 @@ static hipError_t run_batches(const DScene& sc, const DCamera& cam, const WaveAr
         const hipStream_t st = sts[t];
         const uint32_t nslots = sb * a.npix;
         if ((e = mark_begin(plan, uint8_t(KC_EXTEND | (t << KC_TWIN_SHIFT)), st)) != hipSuccess) return e;
-        hipLaunchKernelGGL((k_extend<STACK, kCount, kVol, true, kQuant, kWide>), dim3(gext0[t]), dim3(256), 0, st, sc, cam, a,
+        hipLaunchKernelGGL(k.extend0, dim3(gext0[t]), dim3(256), 0, st, sc, cam, a,
                            a.s[0], a.counts + CNT_STREAM0, a.counts + CNT_STREAM1, a.counts + cnt_shadow(0),
                            a.counts + cnt_fetch_sh(0), a.counts + CNT_FETCH_EXT, sample_base);
         if ((e = mark_end(plan, st)) != hipSuccess) return e;
@@ -1122,23 +1147,15 @@ static hipError_t run_batches(const DScene& sc, const DCamera& cam, const WaveAr
 #endif
         // bounce 0 regenerates the camera rays (no stream), later bounces read s[c]
         if ((e = mark_begin(plan, uint8_t(KC_EXTEND | (t << KC_TWIN_SHIFT)), st)) != hipSuccess) return e;
-        if (b == 0)
-          hipLaunchKernelGGL((k_extend<STACK, kCount, kVol, true, kQuant, kWide>), dim3(gext0[t]), dim3(256), 0, st, sc, cam, a,
-                             a.s[c], cnt_stream[c], cnt_stream[nx], cnt_sh, fetch_sh, fetch_ext, sample_base);
-        else
-          hipLaunchKernelGGL((k_extend<STACK, kCount, kVol, false, kQuant, kWide>), dim3(gext[t]), dim3(256), 0, st, sc, cam, a,
-                             a.s[c], cnt_stream[c], cnt_stream[nx], cnt_sh, fetch_sh, fetch_ext, sample_base);
+        hipLaunchKernelGGL(b == 0 ? k.extend0 : k.extend, dim3(b == 0 ? gext0[t] : gext[t]), dim3(256), 0, st, sc, cam, a,
+                           a.s[c], cnt_stream[c], cnt_stream[nx], cnt_sh, fetch_sh, fetch_ext, sample_base);
         if ((e = mark_end(plan, st)) != hipSuccess) return e;
         RTG_LAUNCHED("k_extend", b, st);
         // k_shade b waits for k_nee_apply b - 1
         if (ovl && b > 0 && (e = hipStreamWaitEvent(st, plan.ev_nee[t], 0)) != hipSuccess) return e;
         if ((e = mark_begin(plan, uint8_t(KC_SHADE | (t << KC_TWIN_SHIFT)), st)) != hipSuccess) return e;
-        if (b == 0)
-          hipLaunchKernelGGL((k_shade<kCount, kEnvIS, kShade, true>), dim3(gsh[t]), dim3(256), shade_lds, st, sc, cam, a, a.s[c],
-                             cnt_stream[c], a.s[nx], cnt_stream[nx], cnt_sh, sample_base, 0u);
-        else
-          hipLaunchKernelGGL((k_shade<kCount, kEnvIS, kShade, false>), dim3(gsh[t]), dim3(256), shade_lds, st, sc, cam, a, a.s[c],
-                             cnt_stream[c], a.s[nx], cnt_stream[nx], cnt_sh, sample_base, uint32_t(b));
+        hipLaunchKernelGGL(b == 0 ? k.shade0 : k.shade, dim3(gsh[t]), dim3(256), shade_lds, st, sc, cam, a, a.s[c],
+                           cnt_stream[c], a.s[nx], cnt_stream[nx], cnt_sh, sample_base, uint32_t(b));
         if ((e = mark_end(plan, st)) != hipSuccess) return e;
         RTG_LAUNCHED("k_shade", b, st);
         // no lights: k_shade writes no NEE job (sampleLightMIS needs a light,
@@ -1149,11 +1166,11 @@ static hipError_t run_batches(const DScene& sc, const DCamera& cam, const WaveAr
             if ((e = hipStreamWaitEvent(sx, plan.ev_shade[t], 0)) != hipSuccess) return e;
           }
           if ((e = mark_begin(plan, uint8_t(KC_SHADOW | (t << KC_TWIN_SHIFT)), sx)) != hipSuccess) return e;
-          hipLaunchKernelGGL((k_shadow<STACK, kCount, kVol, kEnvIS, kQuant, kWide>), dim3(gsd[t]), dim3(256), 0, sx, sc, a,
+          hipLaunchKernelGGL(k.shadow, dim3(gsd[t]), dim3(256), 0, sx, sc, a,
                              cnt_sh, fetch_sh, a.counts + cnt_fetch_sh(nx));
           if ((e = mark_end(plan, sx)) != hipSuccess) return e;
           RTG_LAUNCHED("k_shadow", b, sx);
-          hipLaunchKernelGGL(k_nee_apply<kEnvIS>, dim3(gap[t]), dim3(256), 0, sx, a, cnt_sh);
+          hipLaunchKernelGGL(k.nee_apply, dim3(gap[t]), dim3(256), 0, sx, a, cnt_sh);
           RTG_LAUNCHED("k_nee_apply", b, sx);
           if (ovl && (e = hipEventRecord(plan.ev_nee[t], sx)) != hipSuccess) return e;
         }
@@ -1185,15 +1202,15 @@ static hipError_t run_batches(const DScene& sc, const DCamera& cam, const WaveAr
         if (left == 0) break;
         // few paths left in a render without lights: one k_tail launch per
         // twin carries them to their ends (bit-identical frame)
-        if (!kCount && !nee && plan.tail_rays > 0 && left <= plan.tail_rays && b + 1 < plan.max_depth) {
+        if (k.tail != nullptr && !nee && plan.tail_rays > 0 && left <= plan.tail_rays && b + 1 < plan.max_depth) {
           const size_t lds = shade_lds_bytes(sc);
           const int cap_tail = int(as[0].spill_lanes / 256u);
           for (int t = 0; t < nt; ++t) {
             if (lefts[t] == 0) continue;
             const WaveArgs& a = as[t];
-            int g = grid_for((const void*)k_tail<STACK, kVol, kShade, kQuant, kWide>, 256, lds, lefts[t], cus);
+            int g = grid_for((const void*)k.tail, 256, lds, lefts[t], cus);
             if (g > cap_tail) g = cap_tail;
-            hipLaunchKernelGGL((k_tail<STACK, kVol, kShade, kQuant, kWide>), dim3(g), dim3(256), lds, sts[t], sc, cam, a,
+            hipLaunchKernelGGL(k.tail, dim3(g), dim3(256), lds, sts[t], sc, cam, a,
                                a.s[nx], a.counts + (nx ? CNT_STREAM1 : CNT_STREAM0), a.counts + CNT_FETCH_EXT);
             RTG_LAUNCHED("k_tail", b + 1, sts[t]);
           }
@@ -1206,7 +1223,7 @@ static hipError_t run_batches(const DScene& sc, const DCamera& cam, const WaveAr
     if (ovl)
       for (int t = 0; t < nt; ++t)
         if ((e = hipStreamWaitEvent(sts[t], plan.ev_nee[t], 0)) != hipSuccess) return e;
-    if (!kCount)
+    if (!k.count)
       for (int t = 0; t < nt; ++t) {
         const hipStream_t st = sts[t];
         hipLaunchKernelGGL(k_accum, dim3(grid_for((const void*)k_accum, 256, 0, as[t].npix, cus)), dim3(256), 0, st,
@@ -1233,37 +1250,20 @@ hipError_t guard_report(unsigned int out[4]) {
 }
 #endif
 
-// The variants a scene's traversal and shading compile to: node format (RT_NODES_QUANT8 /
-// RT_NODES_WIDE8 scenes run their node format's own kernels: the default fp32 kernels carry
-// no trace of them; the 8-wide format has no rare-primitive variant, flatten builds it only
-// for scenes that do not need one), importance-sampled HDRI, shading kind.
+// The kernels of the variant the scene runs (wave_variant.h: node format,
+// importance-sampled HDRI, shading kind; RT_NODES_QUANT8 / RT_NODES_WIDE8
+// scenes run their node format's own kernels, the default fp32 kernels carry
+// no trace of them), then the one schedule over them.
 template <int S, bool C, bool V>
 static hipError_t run_variant(const DScene& sc, const DCamera& cam, const WaveArgs* as, const hipStream_t* sts,
                               const WavePlan& plan) {
-  // the importance-sampled HDRI is a NEE light only beside an area light
-  // (sampleLightMIS needs one, camera.go:502): without lights the kEnvIS code
-  // is dead, and its registers spilled (C5: 34 VGPRs in bounce 0's shading)
-  const bool envis = sc.env.valid && sc.env.use_is && sc.num_lights > 0;
-  const int shade = sc.shade_kind | (sc.num_prim_recs > 0 ? SHADE_LIFT : 0);
-  auto by_shade = [&](auto E, auto Q, auto W) {
-    constexpr bool kE = decltype(E)::value, kQ = decltype(Q)::value, kW = decltype(W)::value;
-    if (shade == SHADE_FULL) return run_batches<S, C, V, kE, SHADE_FULL, kQ, kW>(sc, cam, as, sts, plan);
-    if (shade == SHADE_VOL) return run_batches<S, C, V, kE, SHADE_VOL, kQ, kW>(sc, cam, as, sts, plan);
-    if (shade == SHADE_MAT) return run_batches<S, C, V, kE, SHADE_MAT, kQ, kW>(sc, cam, as, sts, plan);
-    // the variants that test the lifted world primitives (lean / material
-    // scenes only, flatten_scene)
-    if (shade == (SHADE_MAT | SHADE_LIFT)) return run_batches<S, C, V, kE, SHADE_MAT | SHADE_LIFT, kQ, kW>(sc, cam, as, sts, plan);
-    if (shade == (SHADE_LEAN | SHADE_LIFT)) return run_batches<S, C, V, kE, SHADE_LEAN | SHADE_LIFT, kQ, kW>(sc, cam, as, sts, plan);
-    return run_batches<S, C, V, kE, SHADE_LEAN, kQ, kW>(sc, cam, as, sts, plan);
-  };
-  auto by_env = [&](auto Q, auto W) {
-    return envis ? by_shade(std::true_type{}, Q, W) : by_shade(std::false_type{}, Q, W);
-  };
-  if constexpr (!V) {
-    if (sc.wide_nodes != 0) return by_env(std::false_type{}, std::true_type{});
-  }
-  if (sc.quant_nodes != 0) return by_env(std::true_type{}, std::false_type{});
-  return by_env(std::false_type{}, std::false_type{});
+  const WaveVariant v = pick_variant(sc);
+  const WaveKernels k = with_nodes<V>(v, [&](auto Q, auto W) {
+    return with_shading(v, [](auto E, auto Sh) {
+      return kernels_for<S, C, V, decltype(E)::value, decltype(Sh)::value, decltype(Q)::value, decltype(W)::value>();
+    });
+  });
+  return run_batches(k, sc, cam, as, sts, plan);
 }
 
 // Each variant group is instantiated in its own translation unit (compiled in
@@ -1304,9 +1304,7 @@ hipError_t launch_wavefront(const DScene& sc, const DCamera& cam, const WaveArgs
       return e;
   }
   if (plan.max_depth > 0) {
-    // the kVol variants also carry the rare primitives (circles)
-    // (and the reference-order closest hit of RotateX/Z scenes, DScene.dfs_order)
-    const bool vol = sc.has_volumes != 0 || sc.n_circles > 0 || sc.dfs_order != 0;
+    const bool vol = pick_variant(sc).vol;   // the translation units split on it
 #ifdef RTG_DIAG_RING
     // diagnostic builds only (RTG_GUARD): one ring size for every
     // scene, no counting variant (a short compile)

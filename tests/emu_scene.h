@@ -29,7 +29,7 @@ struct EmuScene {
   HostScene h;
   std::vector<DNodeQ> qnodes;   // quantised nodes (build.hip k_quantize, same function)
   std::vector<DTriShade> tri_shade;   // shading records (build.hip k_tri_shade, same function)
-  std::vector<DVolRec> vol_recs;        // the lifted volumes' records (api.cpp upload_one, same function)
+  std::vector<DVolRec> vol_recs;        // the lifted volumes' records (build_vol_recs)
   DScene d{};
   DCamera cam{};
   int max_depth = 0;
@@ -70,56 +70,20 @@ static int load_desc(const rt_scene_desc* desc, const rt_camera_desc* c, const F
   d.tri_shade = E.tri_shade.data();
   d.leaves = pad(h.leaves); d.tris = pad(h.tris); d.quads = pad(h.quads); d.spheres = pad(h.spheres);
   // RT_NODES_WIDE8 (RTG_EMU_QUANT=2): the 8-wide arrays, as api.cpp uploads them
-  d.wide_nodes = h.wide_nodes;
-  d.root8 = h.root8;
-  if (h.wide_nodes) {
-    d.nodes8 = pad(h.nodes8); d.litems = pad(h.litems); d.wtris = pad(h.wtris);
-    d.n_nodes8 = uint32_t(h.nodes8.size()); d.n_litems = uint32_t(h.litems.size()); d.n_wtris = uint32_t(h.wtris.size());
-  }
+  if (h.wide_nodes) { d.nodes8 = pad(h.nodes8); d.litems = pad(h.litems); d.wtris = pad(h.wtris); }
   d.quad_wref = ptr(h.quad_wref); d.sphere_wref = ptr(h.sphere_wref);
   d.volumes = ptr(h.volumes); d.vol_refs = ptr(h.vol_refs); d.materials = ptr(h.materials); d.textures = ptr(h.textures);
   d.lights = ptr(h.lights); d.sphere_rank = ptr(h.sphere_rank); d.quad_rank = ptr(h.quad_rank);
   d.tri_rank = ptr(h.tri_rank); d.tlas_ref_top = ptr(h.ref_top); d.sphere_hidx = ptr(h.sphere_hidx);
   d.quad_hidx = ptr(h.quad_hidx); d.tri_hidx = ptr(h.tri_hidx); d.plane_hidx = ptr(h.plane_hidx);
   d.volume_hidx = ptr(h.volume_hidx);
-  d.tlas = h.tlas;
-  d.env.valid = h.env_valid; d.env.width = h.env_w; d.env.height = h.env_h; d.env.use_is = h.env_use_is;
-  d.env.rotation = h.env_rotation; d.env.total_power = h.env_total_power;
   d.env.texels = ptr(h.env_texels); d.env.rgbe = h.env_rgbe.empty() ? nullptr : h.env_rgbe.data(); d.env.pdf = ptr(h.env_pdf); d.env.marginal = ptr(h.env_marginal);
   d.env.conditional = ptr(h.env_conditional);
-  d.num_planes = int(h.planes.size()); d.num_lights = int(h.lights.size());
-  d.num_materials = int(h.materials.size()); d.num_textures = int(h.textures.size());
-  d.stack_needed = h.stack_needed;
-  if (h.wide_nodes && h.stack_needed8 > h.stack_needed) d.stack_needed = h.stack_needed8;   // api.cpp upload_one
-  d.quant_nodes = h.quant_nodes;
-  d.dfs_order = h.dfs_order;
-  d.n_nodes = uint32_t(h.nodes4.size()); d.n_leaves = uint32_t(h.leaves.size()); d.n_refs = uint32_t(h.refs.size());
-  d.n_spheres = uint32_t(h.spheres.size()); d.n_quads = uint32_t(h.quads.size()); d.n_tris = uint32_t(h.tris.size());
-  d.n_instances = uint32_t(h.instances.size()); d.n_blas = uint32_t(h.blas.size());
-  d.n_volumes = uint32_t(h.volumes.size());
-  d.n_circles = uint32_t(h.circles.size());
-  d.shade_kind = SHADE_LEAN;   // the k_shade variant (wavefront.hip)
-  for (const DMaterial& m : h.materials)
-    if (m.kind == RT_METAL || m.kind == RT_DIELECTRIC || m.kind == RT_ISOTROPIC) d.shade_kind = SHADE_MAT;
-  d.needs_uv = 0;
-  for (const DTexture& t : h.textures) {
-    if (t.kind == RT_TEX_IMAGE) d.needs_uv = 1;
-    if (t.kind == RT_TEX_IMAGE || t.kind == RT_TEX_NOISE) d.shade_kind = SHADE_FULL;   // the full tex_value / make_record
-  }
-  // volumes lifted out of the world BVH (flatten: no circles, no Noise /
-  // Image textures) are tested in k_shade's volume variant
-  d.num_vol_refs = int32_t(h.vol_refs.size());
-  d.has_volumes = h.volumes.size() > h.vol_refs.size() ? 1 : 0;
-  if (d.num_vol_refs > 0) d.shade_kind = SHADE_VOL;
-  // tables beyond LDS: the full variant reads them from global memory
-  // (api.cpp upload_one; lifted volumes with such tables are its internal error)
-  if (h.materials.size() > size_t(kLdsMaterials) || h.textures.size() > size_t(kLdsTextures) ||
-      h.lights.size() > size_t(kLdsLights)) {
-    if (d.shade_kind == SHADE_VOL) { fprintf(stderr, "lifted volumes with tables beyond LDS\n"); return 5; }
-    d.shade_kind = SHADE_FULL;
-  }
+  // every scalar of the scene, as rt_scene_upload derives it (flatten.h)
+  if (scene_scalars(h, d, ferr)) { fprintf(stderr, "%s\n", ferr.c_str()); return 5; }
   E.vol_recs = build_vol_recs(h);
   d.vol_recs = E.vol_recs.empty() ? nullptr : E.vol_recs.data();
+  d.prim_recs = ptr(h.prim_recs);
 
   DCamera& cam = E.cam;
   for (int a = 0; a < 3; ++a) {
@@ -148,6 +112,7 @@ static int load(const char* name, int width, const char* asset_dir, EmuScene& E)
   if (rts_scene_create(name, &opt, &E.scn, err, sizeof err) != 0) { fprintf(stderr, "%s\n", err); return 3; }
   FlattenOptions fo;
   if (const char* nf = getenv("RTG_EMU_QUANT")) fo.quant_nodes = atoi(nf);   // node format under test
+  if (const char* lp = getenv("RTG_EMU_LIFT")) fo.lift_prims = atoi(lp);     // world quads / spheres lifted (contexts' default)
   return load_desc(rts_scene_get_desc(E.scn), rts_scene_get_camera(E.scn), fo, E);
 }
 

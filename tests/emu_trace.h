@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "../go-raytracing_amd/csrc/wave_layout.h"
+#include "../go-raytracing_amd/csrc/wave_variant.h"
 
 namespace emu {
 
@@ -98,29 +99,93 @@ static uint32_t shadow_variant(const DScene& sc, WaveArgs a, const float* P, con
 }
 
 // The hit record k_extend stores (store_hit: t, kind << 28 | idx, instance,
-// TLAS ref position) for the ray (o, d), in the kernel variant of the
-// scene's node format.
-static float4 trace_one(const EmuScene& E, TraceArgs& T, const float* o, const float* d) {
+// TLAS ref position) for a path's ray (key: its RNG key) at a given bounce,
+// in the variant the product picks for the scene, with a stack ring of
+// kRingN entries.
+template <int kRingN = kTraceRing>
+static float4 trace_path(const EmuScene& E, TraceArgs& T, const float* o, const float* d, uint32_t key = 0u,
+                         uint32_t bounce = 0u) {
   const float4 ro{o[0], o[1], o[2], 0.0f}, rd{d[0], d[1], d[2], 0.0f};
-  const DScene& sc = E.d;
-  return sc.wide_nodes ? trace_variant<true, false>(sc, E.cam, T.a, ro, rd)
-         : sc.quant_nodes ? trace_variant<false, true>(sc, E.cam, T.a, ro, rd)
-                          : trace_variant<false, false>(sc, E.cam, T.a, ro, rd);
+  return with_traversal(pick_variant(E.d), [&](auto V, auto Q, auto W) {
+    return trace_variant<decltype(W)::value, decltype(Q)::value, decltype(V)::value, kRingN>(E.d, E.cam, T.a, ro, rd, key, bounce);
+  });
 }
 
-// The same for a path's ray at a given bounce, in the variant
-// launch_wavefront picks for the scene: the rare-primitive kernels when a
-// volume is left in the world BVH, a circle exists or the scene traverses in
-// reference order (they have no 8-wide form), else the node format's own.
-static float4 trace_path(const EmuScene& E, TraceArgs& T, const float* o, const float* d, uint32_t key, uint32_t bounce) {
-  const float4 ro{o[0], o[1], o[2], 0.0f}, rd{d[0], d[1], d[2], 0.0f};
-  const DScene& sc = E.d;
-  if (sc.has_volumes != 0 || sc.n_circles > 0 || sc.dfs_order != 0)
-    return sc.quant_nodes ? trace_variant<false, true, true>(sc, E.cam, T.a, ro, rd, key, bounce)
-                          : trace_variant<false, false, true>(sc, E.cam, T.a, ro, rd, key, bounce);
-  return sc.wide_nodes ? trace_variant<true, false>(sc, E.cam, T.a, ro, rd, key, bounce)
-         : sc.quant_nodes ? trace_variant<false, true>(sc, E.cam, T.a, ro, rd, key, bounce)
-                          : trace_variant<false, false>(sc, E.cam, T.a, ro, rd, key, bounce);
+// One shadow ray of a path through k_shadow in the same variant
+// (shadow_variant's visibility word).
+template <int kRingN = kTraceRing>
+static uint32_t shadow_path(const EmuScene& E, TraceArgs& T, const float* P, const float* dir, float tmax, uint32_t key,
+                            uint32_t bounce) {
+  return with_traversal(pick_variant(E.d), [&](auto V, auto Q, auto W) {
+    return shadow_variant<decltype(W)::value, decltype(Q)::value, decltype(V)::value, kRingN>(E.d, T.a, P, dir, tmax, key, bounce);
+  });
+}
+
+// A hit record's words, and the hittable ids it names as rt_primary_hits
+// reports them (probe.hip hit_ids; top = prim = -1 and t = -1 for a miss).
+struct Hit {
+  uint32_t kh;   // kind << 28 | idx, 0: a miss
+  float t;
+  int inst, refpos;
+};
+static Hit unpack(float4 h) {
+  uint32_t w[4];
+  std::memcpy(w, &h, 16);
+  return Hit{w[1], h.x, int(w[2]), int(w[3])};
+}
+static void hit_ids(const DScene& sc, const Hit& h, int32_t& top, int32_t& prim, float& t) {
+  top = prim = -1;
+  t = -1.0f;
+  if (h.kh == 0u) return;
+  const int kind = int(h.kh >> 28), idx = int(h.kh & 0x0FFFFFFFu);
+  t = h.t;
+  if (kind == PK_PLANE) { top = prim = sc.plane_hidx[idx]; return; }
+  top = sc.tlas_ref_top[h.refpos];
+  prim = kind == PK_SPHERE ? sc.sphere_hidx[idx] : kind == PK_QUAD ? sc.quad_hidx[idx] : kind == PK_TRI ? sc.tri_hidx[idx]
+         : kind == PK_CIRCLE ? sc.circle_hidx[idx] : sc.volume_hidx[idx];
+}
+
+// What shade_path and the path probe add to k_extend's hit: the lifted
+// volumes' and the lifted world primitives' tests.
+static void merge_lifted(const DScene& sc, Hit& r, V3 ro, V3 rd, uint32_t key, uint32_t bounce) {
+  Cnt cnt = {};
+  if (sc.num_vol_refs > 0) lifted_volumes<false>(sc, ro, rd, key, bounce, r.kh, r.t, r.inst, r.refpos, cnt, sc.vol_recs);
+  if (sc.num_prim_recs > 0) lifted_prims<false>(sc, ro, rd, ray_time(key), r.kh, r.t, r.inst, r.refpos, cnt);
+}
+
+// The closest hit of one path ray as the pipeline finds it.
+static Hit closest(const EmuScene& E, TraceArgs& T, const float* o, const float* d, uint32_t key, uint32_t bounce) {
+  Hit r = unpack(trace_path(E, T, o, d, key, bounce));
+  merge_lifted(E.d, r, mk(o[0], o[1], o[2]), mk(d[0], d[1], d[2]), key, bounce);
+  return r;
+}
+
+// One path's bounce through the production shade_path in the variant the
+// scene runs (wave_variant.h; kFirst at bounce 0) with a one-slot Lout: what
+// shade_path decides, and L, the radiance it added.
+struct Shaded {
+  bool cont = false, want_shadow = false, lout_set = false;
+  uint32_t flags = 0, nstate = 0;
+  float tmax_a = 0.0f;
+  V3 P{}, sd{}, nbeta{}, ca{}, ch{}, da{}, dh{};
+  float4 L{};
+};
+static Shaded shade_by_kind(const EmuScene& E, TraceArgs& T, float4 h, V3 ro, V3 rd, V3 beta, uint32_t key, int dleft,
+                            uint32_t bounce, bool allow) {
+  Shaded r;
+  Cnt cnt = {};
+  T.a.Lout[0] = float4{0.0f, 0.0f, 0.0f, 0.0f};
+  with_shading(pick_variant(E.d), [&](auto H, auto S) {
+    auto go = [&](auto F) {
+      shade_path<false, decltype(H)::value, decltype(S)::value, decltype(F)::value>(
+          E.d, E.cam, T.a, E.d.vol_recs, h, ro, rd, beta, key, 0u, dleft, bounce, allow, r.cont, r.want_shadow, r.flags,
+          r.nstate, r.tmax_a, r.P, r.sd, r.nbeta, r.ca, r.ch, r.da, r.dh, r.lout_set, cnt);
+    };
+    if (bounce == 0) go(std::true_type{}); else go(std::false_type{});
+  });
+  if (!r.want_shadow) r.flags = 0u;
+  r.L = T.a.Lout[0];
+  return r;
 }
 
 }  // namespace emu

@@ -33,21 +33,6 @@
 
 using namespace rtg;
 
-namespace {
-
-// probe.hip hit_ids
-void hit_ids(const DScene& sc, int kind, int idx, int refpos, int32_t& top, int32_t& prim) {
-  if (kind == PK_PLANE) { top = prim = sc.plane_hidx[idx]; return; }
-  top = sc.tlas_ref_top[refpos];
-  if (kind == PK_SPHERE) prim = sc.sphere_hidx[idx];
-  else if (kind == PK_QUAD) prim = sc.quad_hidx[idx];
-  else if (kind == PK_TRI) prim = sc.tri_hidx[idx];
-  else if (kind == PK_CIRCLE) prim = sc.circle_hidx[idx];
-  else prim = sc.volume_hidx[idx];
-}
-
-}  // namespace
-
 // Closest hits of n rays (o, d: n * 3 floats each) in the scene `desc`,
 // flattened with the given world-BVH builder, mesh builder (BLAS_REFERENCE /
 // BLAS_SAH) and node format (0 fp32, 1 quant8, 2 wide8; *format_used: what the
@@ -64,22 +49,14 @@ extern "C" int hits_emu_run(const rt_scene_desc* desc, const rt_camera_desc* cam
   fo.quant_nodes = node_format;
   if (int rc = emu::load_desc(desc, cam, fo, E)) return rc;
   const DScene& sc = E.d;
-  if (sc.has_volumes || sc.num_vol_refs > 0 || sc.n_circles > 0 || sc.dfs_order) {
+  if (pick_variant(sc).vol || sc.num_vol_refs > 0) {
     fprintf(stderr, "hits_emu: rare-primitive scenes are not supported\n");
     return 3;
   }
   *format_used = sc.wide_nodes ? 2 : sc.quant_nodes ? 1 : 0;
   emu::TraceArgs T(E.max_depth, int(E.d.stack_needed));
   for (int i = 0; i < n; ++i) {
-    const float4 h = emu::trace_one(E, T, o + 3 * i, d + 3 * i);
-    uint32_t w[4];
-    memcpy(w, &h, 16);
-    top[i] = prim[i] = -1;
-    t[i] = -1.0f;
-    if (w[1] != 0u) {
-      hit_ids(sc, int(w[1] >> 28), int(w[1] & 0x0FFFFFFFu), int(w[3]), top[i], prim[i]);
-      t[i] = h.x;
-    }
+    emu::hit_ids(sc, emu::unpack(emu::trace_path(E, T, o + 3 * i, d + 3 * i)), top[i], prim[i], t[i]);
   }
   return T.err ? 6 : 0;
 }
@@ -104,7 +81,7 @@ extern "C" int hits_emu_placement(const rt_scene_desc* desc, const rt_camera_des
   out[2] = sc.shade_kind;
   out[3] = int32_t(E.vol_recs.size());
   out[4] = sc.needs_uv;
-  out[5] = (sc.has_volumes != 0 || sc.n_circles > 0 || sc.dfs_order != 0) ? 1 : 0;
+  out[5] = pick_variant(sc).vol ? 1 : 0;
   out[6] = sc.wide_nodes ? 2 : sc.quant_nodes ? 1 : 0;
   out[7] = int32_t(sc.n_volumes);
   for (int i = 0; i < kVolRecMax * kVolRecQuads; ++i) codes[i] = 0u;
@@ -131,7 +108,7 @@ extern "C" int hits_emu_flatten_status(const rt_scene_desc* desc, int lift_volum
 
 // Closest hits of n path rays at bounce `bounce` (pix[i]: the path's pixel;
 // the RNG key is production's for (seed, pixel, sample)), as the pipeline
-// finds them: k_extend in the variant launch_wavefront picks (volumes left in
+// finds them: k_extend in the variant pick_variant names (volumes left in
 // the world BVH are tested there), then the lifted volumes' test as k_shade
 // and the path probe apply it (lifted_volumes).  Any scene the flattener
 // takes.  lift_volumes: RT_VOLUMES_LIFTED (1) or RT_VOLUMES_IN_BVH (0).
@@ -151,65 +128,12 @@ extern "C" int hits_emu_run_paths(const rt_scene_desc* desc, const rt_camera_des
   emu::TraceArgs T(E.max_depth, int(E.d.stack_needed));
   for (int i = 0; i < n; ++i) {
     const uint32_t key = path_key(seed, uint32_t(pix[i]), sample);
-    const float4 h = emu::trace_path(E, T, o + 3 * i, d + 3 * i, key, uint32_t(bounce));
-    uint32_t w[4];
-    memcpy(w, &h, 16);
-    uint32_t kh = w[1];
-    float ht = h.x;
-    int hinst = int(w[2]), hrefpos = int(w[3]);
-    Cnt cnt = {};
-    if (sc.num_vol_refs > 0)
-      lifted_volumes<false>(sc, mk(o[3 * i], o[3 * i + 1], o[3 * i + 2]), mk(d[3 * i], d[3 * i + 1], d[3 * i + 2]), key,
-                            uint32_t(bounce), kh, ht, hinst, hrefpos, cnt, sc.vol_recs);
-    top[i] = prim[i] = -1;
-    t[i] = -1.0f;
-    if (kh != 0u) {
-      hit_ids(sc, int(kh >> 28), int(kh & 0x0FFFFFFFu), hrefpos, top[i], prim[i]);
-      t[i] = ht;
-    }
+    emu::hit_ids(sc, emu::closest(E, T, o + 3 * i, d + 3 * i, key, uint32_t(bounce)), top[i], prim[i], t[i]);
   }
   return T.err ? 6 : 0;
 }
 
-namespace {
-
-struct ShadeOut {
-  int32_t* cont; float* P; float* sd; float* nbeta; float* Ladd; uint32_t* flags;
-  float* ca; float* da; float* tmax_a; float* ch; float* dh;
-};
-
-void put3(float* dst, int i, const V3& v) { dst[3 * i] = v.x; dst[3 * i + 1] = v.y; dst[3 * i + 2] = v.z; }
-
-template <bool kEnvIS, int kShade, bool kFirst>
-void shade_one(const emu::EmuScene& E, emu::TraceArgs& T, float4 h, V3 ro, V3 rd, V3 beta, uint32_t key, int dleft,
-               uint32_t bounce, bool allow, int i, const ShadeOut& out) {
-  bool cont = false, want_shadow = false, lout_set = false;
-  uint32_t flags = 0, nstate = 0;
-  float tmax_a = 0.0f;
-  V3 P = mk(0.0f, 0.0f, 0.0f), sd = P, nbeta = P, ca = P, ch = P, da = P, dh = P;
-  Cnt cnt = {};
-  T.a.Lout[0] = float4{0.0f, 0.0f, 0.0f, 0.0f};
-  shade_path<false, kEnvIS, kShade, kFirst>(E.d, E.cam, T.a, E.d.vol_recs, h, ro, rd, beta, key, 0u, dleft, bounce, allow,
-                                            cont, want_shadow, flags, nstate, tmax_a, P, sd, nbeta, ca, ch, da, dh,
-                                            lout_set, cnt);
-  out.cont[i] = cont ? 1 : 0;
-  out.flags[i] = want_shadow ? flags : 0u;
-  out.tmax_a[i] = tmax_a;
-  put3(out.P, i, P); put3(out.sd, i, sd); put3(out.nbeta, i, nbeta); put3(out.ca, i, ca); put3(out.da, i, da);
-  put3(out.ch, i, ch); put3(out.dh, i, dh);
-  const float4 L = T.a.Lout[0];
-  put3(out.Ladd, i, lout_set ? mk(L.x, L.y, L.z) : mk(0.0f, 0.0f, 0.0f));
-}
-
-template <bool kEnvIS, bool kFirst, class... A>
-void shade_by_kind(int shade, A&&... args) {
-  if (shade == SHADE_FULL) shade_one<kEnvIS, SHADE_FULL, kFirst>(args...);
-  else if (shade == SHADE_VOL) shade_one<kEnvIS, SHADE_VOL, kFirst>(args...);
-  else if (shade == SHADE_MAT) shade_one<kEnvIS, SHADE_MAT, kFirst>(args...);
-  else shade_one<kEnvIS, SHADE_LEAN, kFirst>(args...);
-}
-
-}  // namespace
+static void put3(float* dst, int i, const V3& v) { dst[3 * i] = v.x; dst[3 * i + 1] = v.y; dst[3 * i + 2] = v.z; }
 
 // How the flattener hands the environment's texels to the device: 1 RGBE
 // words (every texel re-encodes exactly), 0 fp32 texels, -1 no environment;
@@ -224,7 +148,7 @@ extern "C" int hits_emu_env_format(const rt_scene_desc* desc, const rt_camera_de
 
 // One bounce of n paths through the production pipeline's two halves: the
 // closest hit as hits_emu_run_paths finds it (k_extend, one lane), then
-// shade_path in the variant run_variant picks for the scene (shade_kind, the
+// shade_path in the variant pick_variant names for the scene (shade kind, the
 // importance-sampled HDRI only beside a light, kFirst at bounce 0), with a
 // one-slot Lout.  Per path: seed / sample / pix[i] key it, (o, d, beta) are
 // its incoming ray and throughput, dleft the depth left, allow whether an
@@ -246,9 +170,7 @@ extern "C" int hits_emu_shade(const rt_scene_desc* desc, const rt_camera_desc* c
   if (int rc = emu::load_desc(desc, cam, fo, E)) return rc;
   if (!o && bounce != 0) return 2;
   const DScene& sc = E.d;
-  const bool envis = sc.env.valid && sc.env.use_is && sc.num_lights > 0;   // run_variant
   emu::TraceArgs T(E.max_depth, int(E.d.stack_needed));
-  const ShadeOut out{cont, P, sd, nbeta, Ladd, flags, ca, da, tmax_a, ch, dh};
   for (int i = 0; i < n; ++i) {
     const uint32_t key = path_key(seed, uint32_t(pix[i]), sample);
     V3 ro, rd;
@@ -262,52 +184,35 @@ extern "C" int hits_emu_shade(const rt_scene_desc* desc, const rt_camera_desc* c
     if (ray) { put3(ray, 2 * i, ro); put3(ray, 2 * i + 1, rd); }
     const float fo3[3] = {ro.x, ro.y, ro.z}, fd3[3] = {rd.x, rd.y, rd.z};
     const float4 h = emu::trace_path(E, T, fo3, fd3, key, uint32_t(bounce));
-    uint32_t w[4];
-    memcpy(w, &h, 16);
-    {   // the hit reported: with the lifted volumes' test applied, as shade_path applies it to its own copy
-      uint32_t kh = w[1];
-      float ht = h.x;
-      int hinst = int(w[2]), hrefpos = int(w[3]);
-      Cnt c0 = {};
-      if (sc.num_vol_refs > 0) lifted_volumes<false>(sc, ro, rd, key, uint32_t(bounce), kh, ht, hinst, hrefpos, c0, sc.vol_recs);
-      hit[i] = kh != 0u ? 1 : 0;
-      t[i] = kh != 0u ? ht : -1.0f;
+    {   // the hit reported: with the lifted tests applied, as shade_path applies them to its own copy
+      emu::Hit m = emu::unpack(h);
+      emu::merge_lifted(sc, m, ro, rd, key, uint32_t(bounce));
+      hit[i] = m.kh != 0u ? 1 : 0;
+      t[i] = m.kh != 0u ? m.t : -1.0f;
     }
-    const V3 b = mk(beta[3 * i], beta[3 * i + 1], beta[3 * i + 2]);
-    const uint32_t bn = uint32_t(bounce);
-    if (envis) {
-      if (bounce == 0) shade_by_kind<true, true>(sc.shade_kind, E, T, h, ro, rd, b, key, dleft, bn, allow != 0, i, out);
-      else shade_by_kind<true, false>(sc.shade_kind, E, T, h, ro, rd, b, key, dleft, bn, allow != 0, i, out);
-    } else {
-      if (bounce == 0) shade_by_kind<false, true>(sc.shade_kind, E, T, h, ro, rd, b, key, dleft, bn, allow != 0, i, out);
-      else shade_by_kind<false, false>(sc.shade_kind, E, T, h, ro, rd, b, key, dleft, bn, allow != 0, i, out);
-    }
+    const emu::Shaded r = emu::shade_by_kind(E, T, h, ro, rd, mk(beta[3 * i], beta[3 * i + 1], beta[3 * i + 2]), key, dleft,
+                                             uint32_t(bounce), allow != 0);
+    cont[i] = r.cont ? 1 : 0;
+    flags[i] = r.flags;
+    tmax_a[i] = r.tmax_a;
+    put3(P, i, r.P); put3(sd, i, r.sd); put3(nbeta, i, r.nbeta); put3(ca, i, r.ca); put3(da, i, r.da);
+    put3(ch, i, r.ch); put3(dh, i, r.dh);
+    put3(Ladd, i, r.lout_set ? mk(r.L.x, r.L.y, r.L.z) : mk(0.0f, 0.0f, 0.0f));
   }
   return T.err ? 6 : 0;
 }
 
 // One frame of the description through the production wavefront pipeline on
 // the host (wave_run.h: camera -> extend -> shade -> shadow -> NEE apply ->
-// accumulate -> finalize, the kernel variants run_variant picks, one batch):
+// accumulate -> finalize, the kernel variants pick_variant names, one batch):
 // spp samples from sample_offset to `depth` (rt_render_params), the camera's
 // own max_depth kept for the phantom-HDRI rule.  out: H * W * 3 float sums,
 // what rt_render returns.  volumes_in_bvh: RT_OPT_VOLUMES' value,
 // RT_VOLUMES_LIFTED (0) or RT_VOLUMES_IN_BVH (1).  Returns 0, load_desc's code, or
 // 6 when a kernel flagged an internal error.
-extern "C" int hits_emu_render_opts(const rt_scene_desc* desc, const rt_camera_desc* cam, int node_format, int tlas_builder,
-                                    uint32_t seed, uint32_t sample_offset, int spp, int depth, float* out,
-                                    int volumes_in_bvh, int32_t* format_used);
-
-extern "C" int hits_emu_render(const rt_scene_desc* desc, const rt_camera_desc* cam, int node_format, uint32_t seed,
-                               uint32_t sample_offset, int spp, int depth, float* out, int volumes_in_bvh) {
-  int32_t used = 0;
-  return hits_emu_render_opts(desc, cam, node_format, FlattenOptions().tlas_builder, seed, sample_offset, spp, depth, out,
-                              volumes_in_bvh, &used);
-}
-
-// hits_emu_render with the world-BVH builder the caller names (BLAS_REFERENCE
-// / BLAS_SAH); *format_used: the node format the scene took, as
-// hits_emu_run reports it (tests/test_xform_kat.py).
+// (hits_emu_render_opts: with the world-BVH builder the caller names,
+// BLAS_REFERENCE / BLAS_SAH, and *format_used, the node format the scene
+// took as hits_emu_run reports it; tests/test_xform_kat.py.)
 extern "C" int hits_emu_render_opts(const rt_scene_desc* desc, const rt_camera_desc* cam, int node_format, int tlas_builder,
                                     uint32_t seed, uint32_t sample_offset, int spp, int depth, float* out,
                                     int volumes_in_bvh, int32_t* format_used) {
@@ -319,11 +224,17 @@ extern "C" int hits_emu_render_opts(const rt_scene_desc* desc, const rt_camera_d
   if (int rc = emu::load_desc(desc, cam, fo, E)) return rc;
   const DScene& sc = E.d;
   *format_used = sc.wide_nodes ? 2 : sc.quant_nodes ? 1 : 0;
-  const bool envis = sc.env.valid && sc.env.use_is && sc.num_lights > 0;   // run_variant
   std::vector<float> frame;
-  const int err = wave_run::render(E, seed, sample_offset, uint32_t(spp), uint32_t(spp), depth, envis, frame, nullptr);
+  const int err = wave_run::render(E, seed, sample_offset, uint32_t(spp), uint32_t(spp), depth, frame, nullptr);
   memcpy(out, frame.data(), frame.size() * sizeof(float));
   return err ? 6 : 0;
+}
+
+extern "C" int hits_emu_render(const rt_scene_desc* desc, const rt_camera_desc* cam, int node_format, uint32_t seed,
+                               uint32_t sample_offset, int spp, int depth, float* out, int volumes_in_bvh) {
+  int32_t used = 0;
+  return hits_emu_render_opts(desc, cam, node_format, FlattenOptions().tlas_builder, seed, sample_offset, spp, depth, out,
+                              volumes_in_bvh, &used);
 }
 
 // ---- the traversal stack bound (tests/test_stack_host.py) -------------------
@@ -347,30 +258,6 @@ struct PeakArea {
   }
 };
 
-template <int R>
-float4 closest_ring(const emu::EmuScene& E, WaveArgs a, const float* o, const float* d, uint32_t key, uint32_t bounce) {
-  const float4 ro{o[0], o[1], o[2], 0.0f}, rd{d[0], d[1], d[2], 0.0f};
-  const DScene& sc = E.d;
-  if (sc.has_volumes != 0 || sc.n_circles > 0 || sc.dfs_order != 0)   // emu::trace_path's rule
-    return sc.quant_nodes ? emu::trace_variant<false, true, true, R>(sc, E.cam, a, ro, rd, key, bounce)
-                          : emu::trace_variant<false, false, true, R>(sc, E.cam, a, ro, rd, key, bounce);
-  return sc.wide_nodes ? emu::trace_variant<true, false, false, R>(sc, E.cam, a, ro, rd, key, bounce)
-         : sc.quant_nodes ? emu::trace_variant<false, true, false, R>(sc, E.cam, a, ro, rd, key, bounce)
-                          : emu::trace_variant<false, false, false, R>(sc, E.cam, a, ro, rd, key, bounce);
-}
-
-template <int R>
-uint32_t anyhit_ring(const emu::EmuScene& E, WaveArgs a, const float* o, const float* d, float tmax, uint32_t key,
-                     uint32_t bounce) {
-  const DScene& sc = E.d;
-  if (sc.has_volumes != 0 || sc.n_circles > 0 || sc.dfs_order != 0)
-    return sc.quant_nodes ? emu::shadow_variant<false, true, true, R>(sc, a, o, d, tmax, key, bounce)
-                          : emu::shadow_variant<false, false, true, R>(sc, a, o, d, tmax, key, bounce);
-  return sc.wide_nodes ? emu::shadow_variant<true, false, false, R>(sc, a, o, d, tmax, key, bounce)
-         : sc.quant_nodes ? emu::shadow_variant<false, true, false, R>(sc, a, o, d, tmax, key, bounce)
-                          : emu::shadow_variant<false, false, false, R>(sc, a, o, d, tmax, key, bounce);
-}
-
 }  // namespace
 
 // What the flattener derives for the traversal stack.  out[0]: flatten_scene's
@@ -378,7 +265,7 @@ uint32_t anyhit_ring(const emu::EmuScene& E, WaveArgs a, const float* o, const f
 // blas_need4, [4] max_leaf_inst, [5] dfs_order, [6] the node format taken, [7]
 // stack_needed8, [8] tlas_need8, [9] blas_need8 (the 8-wide figures only
 // where that format is taken), [10] BVH4 nodes, [11] 8-wide nodes, [12] BLASes,
-// [13] the bound the kernels' spill area is sized from (api.cpp upload_one).
+// [13] the bound the kernels' spill area is sized from (scene_scalars).
 // nodes4 (cap4 nodes x 5 words: the four child items, then the mask of used
 // slots), nodes8 (cap8 x 32 words: the records as they are) and roots (the
 // world root item in both forms, then per BLAS its root item in both forms;
@@ -398,7 +285,9 @@ extern "C" int hits_emu_stack_info(const rt_scene_desc* desc, int tlas_builder, 
   out[6] = h.wide_nodes ? 2 : h.quant_nodes ? 1 : 0;
   out[7] = h.stack_needed8; out[8] = h.tlas_need8; out[9] = h.blas_need8;
   out[10] = int32_t(h.nodes4.size()); out[11] = int32_t(h.nodes8.size()); out[12] = int32_t(h.blas.size());
-  out[13] = h.wide_nodes ? std::max(h.stack_needed, h.stack_needed8) : h.stack_needed;
+  DScene d{};
+  scene_scalars(h, d, err);
+  out[13] = d.stack_needed;
   const float inf = std::numeric_limits<float>::infinity();
   if (nodes4)
     for (size_t i = 0; i < h.nodes4.size() && i < size_t(cap4); ++i) {
@@ -425,7 +314,7 @@ extern "C" int hits_emu_stack_info(const rt_scene_desc* desc, int tlas_builder, 
 // n rays through the production kernels with the smallest ring the host
 // pipeline runs with, and each ray's peak stack depth in words, read off the
 // spill area (PeakArea).  any == 0: closest hits (k_extend in the variant
-// launch_wavefront picks, the rare-primitive / reference-order one included;
+// pick_variant names, the rare-primitive / reference-order one included;
 // top / prim / t as hits_emu_run_paths); any == 1: shadow rays from o along d
 // to tmax[i] through k_shadow (vis[i]: 1 the ray passed).  tight == 1: the
 // kernels see the product's spill capacity, spill_cap_for(the scene's bound,
@@ -456,17 +345,10 @@ extern "C" int hits_emu_stack_trace(const rt_scene_desc* desc, const rt_camera_d
   for (int i = 0; i < n; ++i) {
     area.reset();
     if (any) {
-      vis[i] = int32_t(anyhit_ring<kPeakRing>(E, T.a, o + 3 * i, d + 3 * i, tmax[i], 0u, uint32_t(bounce)) & 1u);
+      vis[i] = int32_t(emu::shadow_path<kPeakRing>(E, T, o + 3 * i, d + 3 * i, tmax[i], 0u, uint32_t(bounce)) & 1u);
     } else {
-      const float4 h = closest_ring<kPeakRing>(E, T.a, o + 3 * i, d + 3 * i, 0u, uint32_t(bounce));
-      uint32_t w[4];
-      memcpy(w, &h, 16);
-      top[i] = prim[i] = -1;
-      t[i] = -1.0f;
-      if (w[1] != 0u) {
-        hit_ids(sc, int(w[1] >> 28), int(w[1] & 0x0FFFFFFFu), int(w[3]), top[i], prim[i]);
-        t[i] = h.x;
-      }
+      emu::hit_ids(sc, emu::unpack(emu::trace_path<kPeakRing>(E, T, o + 3 * i, d + 3 * i, 0u, uint32_t(bounce))), top[i], prim[i],
+                   t[i]);
     }
     const int k = area.top();
     peak[i] = k < 0 ? 0 : k + kPeakRing + 1;
@@ -521,7 +403,7 @@ extern "C" int hits_emu_render_blas(const rt_scene_desc* desc, const rt_camera_d
   info[1] = int32_t(sc.stack_needed);
   info[2] = spill_cap_for(int(sc.stack_needed), wave_run::kRing);
   std::vector<float> frame;
-  const int err = wave_run::render(E, seed, 0u, uint32_t(spp), uint32_t(spp), depth, false, frame, nullptr);
+  const int err = wave_run::render(E, seed, 0u, uint32_t(spp), uint32_t(spp), depth, frame, nullptr);
   memcpy(out, frame.data(), frame.size() * sizeof(float));
   return err ? 6 : 0;
 }

@@ -29,34 +29,14 @@ using namespace rtg;
 
 namespace {
 
-// probe.hip hit_ids
-void hit_ids(const DScene& sc, int kind, int idx, int refpos, int32_t& top, int32_t& prim) {
-  if (kind == PK_PLANE) { top = prim = sc.plane_hidx[idx]; return; }
-  top = sc.tlas_ref_top[refpos];
-  if (kind == PK_SPHERE) prim = sc.sphere_hidx[idx];
-  else if (kind == PK_QUAD) prim = sc.quad_hidx[idx];
-  else if (kind == PK_TRI) prim = sc.tri_hidx[idx];
-  else if (kind == PK_CIRCLE) prim = sc.circle_hidx[idx];
-  else prim = sc.volume_hidx[idx];
-}
-
-// The description flattened as a context flattens it (tlas_builder, node
-// format, lift_prims), and the lifted records handed to the kernels' scene
-// the way api.cpp upload_one hands them over.
+// The description flattened as a context flattens it.
 int load(const rt_scene_desc* desc, const rt_camera_desc* cam, int tlas_builder, int node_format, int lift,
          emu::EmuScene& E) {
   FlattenOptions fo;
   fo.tlas_builder = tlas_builder;
   fo.quant_nodes = node_format;
   fo.lift_prims = lift;
-  if (int rc = emu::load_desc(desc, cam, fo, E)) return rc;
-  E.d.num_prim_recs = int32_t(E.h.prim_recs.size());
-  E.d.prim_recs = E.h.prim_recs.empty() ? nullptr : E.h.prim_recs.data();
-  if (E.d.num_prim_recs > 0 && E.d.shade_kind != SHADE_LEAN && E.d.shade_kind != SHADE_MAT) {
-    fprintf(stderr, "lift_emu: lifted primitives in a scene without a lift shading variant\n");
-    return 5;
-  }
-  return 0;
+  return emu::load_desc(desc, cam, fo, E);
 }
 
 int format_of(const DScene& sc) { return sc.wide_nodes ? 2 : sc.quant_nodes ? 1 : 0; }
@@ -119,74 +99,6 @@ void world_prims_in_bvh(const HostScene& h, int& inline_items, int& leaf_refs, i
       if (tag_of(it) == ITEM_WQUAD || tag_of(it) == ITEM_WSPHERE) inline_items8++;
     if (tag_of(h.root8) == ITEM_WQUAD || tag_of(h.root8) == ITEM_WSPHERE) inline_items8++;
   }
-}
-
-struct Hit {
-  uint32_t kh;
-  float t;
-  int inst, refpos;
-};
-
-// The closest hit of one path ray as the pipeline finds it: k_extend in the
-// variant launch_wavefront picks, then the lifted primitives' merge as
-// shade_path / the path probe apply it.
-Hit closest(const emu::EmuScene& E, emu::TraceArgs& T, const float* o, const float* d, uint32_t key, uint32_t bounce) {
-  const float4 h = emu::trace_path(E, T, o, d, key, bounce);
-  uint32_t w[4];
-  memcpy(w, &h, 16);
-  Hit r{w[1], h.x, int(w[2]), int(w[3])};
-  Cnt cnt = {};
-  const V3 ro = mk(o[0], o[1], o[2]), rd = mk(d[0], d[1], d[2]);
-  if (E.d.num_vol_refs > 0) lifted_volumes<false>(E.d, ro, rd, key, bounce, r.kh, r.t, r.inst, r.refpos, cnt, E.d.vol_recs);
-  if (E.d.num_prim_recs > 0)
-    lifted_prims<false>(E.d, ro, rd, ray_time(key), r.kh, r.t, r.inst, r.refpos, cnt);
-  return r;
-}
-
-// One shadow ray through k_shadow in the variant launch_wavefront picks
-// (emu::trace_path's rule): 1 = the ray passed.
-uint32_t shadow(const emu::EmuScene& E, emu::TraceArgs& T, const float* P, const float* dir, float tmax, uint32_t key,
-                uint32_t bounce) {
-  const DScene& sc = E.d;
-  constexpr int R = emu::kTraceRing;
-  if (sc.has_volumes != 0 || sc.n_circles > 0 || sc.dfs_order != 0)
-    return (sc.quant_nodes ? emu::shadow_variant<false, true, true, R>(sc, T.a, P, dir, tmax, key, bounce)
-                           : emu::shadow_variant<false, false, true, R>(sc, T.a, P, dir, tmax, key, bounce)) & 1u;
-  return (sc.wide_nodes ? emu::shadow_variant<true, false, false, R>(sc, T.a, P, dir, tmax, key, bounce)
-          : sc.quant_nodes ? emu::shadow_variant<false, true, false, R>(sc, T.a, P, dir, tmax, key, bounce)
-                           : emu::shadow_variant<false, false, false, R>(sc, T.a, P, dir, tmax, key, bounce)) & 1u;
-}
-
-struct NeeOut {
-  uint32_t flags;   // the rays the job carries (bit 0 area, 1 HDRI), after the lifted primitives' tests
-  float tmax_a;
-  V3 P, da, dh;
-};
-
-template <bool kEnvIS, int kShadeL, bool kFirst>
-NeeOut shade_one(const emu::EmuScene& E, emu::TraceArgs& T, float4 h, V3 ro, V3 rd, uint32_t key, int dleft, uint32_t bounce) {
-  bool cont = false, want_shadow = false, lout_set = false;
-  uint32_t flags = 0, nstate = 0;
-  float tmax_a = 0.0f;
-  V3 P = mk(0.0f, 0.0f, 0.0f), sd = P, nbeta = P, ca = P, ch = P, da = P, dh = P;
-  Cnt cnt = {};
-  T.a.Lout[0] = float4{0.0f, 0.0f, 0.0f, 0.0f};
-  shade_path<false, kEnvIS, kShadeL, kFirst>(E.d, E.cam, T.a, E.d.vol_recs, h, ro, rd, mk(1.0f, 1.0f, 1.0f), key, 0u, dleft,
-                                             bounce, true, cont, want_shadow, flags, nstate, tmax_a, P, sd, nbeta, ca, ch, da,
-                                             dh, lout_set, cnt);
-  return NeeOut{want_shadow ? flags : 0u, tmax_a, P, da, dh};
-}
-
-// shade_path in the variant run_variant picks (wavefront.hip by_shade)
-template <bool kEnvIS, bool kFirst, class... A>
-NeeOut shade_by_kind(const DScene& sc, A&&... args) {
-  const int shade = sc.shade_kind | (sc.num_prim_recs > 0 ? SHADE_LIFT : 0);
-  if (shade == SHADE_FULL) return shade_one<kEnvIS, SHADE_FULL, kFirst>(args...);
-  if (shade == SHADE_VOL) return shade_one<kEnvIS, SHADE_VOL, kFirst>(args...);
-  if (shade == SHADE_MAT) return shade_one<kEnvIS, SHADE_MAT, kFirst>(args...);
-  if (shade == (SHADE_MAT | SHADE_LIFT)) return shade_one<kEnvIS, SHADE_MAT | SHADE_LIFT, kFirst>(args...);
-  if (shade == (SHADE_LEAN | SHADE_LIFT)) return shade_one<kEnvIS, SHADE_LEAN | SHADE_LIFT, kFirst>(args...);
-  return shade_one<kEnvIS, SHADE_LEAN, kFirst>(args...);
 }
 
 }  // namespace
@@ -253,12 +165,10 @@ extern "C" int lift_emu_paths(const rt_scene_desc* desc, const rt_camera_desc* c
   emu::TraceArgs T(E.max_depth, int(sc.stack_needed));
   for (int i = 0; i < n; ++i) {
     const uint32_t key = path_key(seed, uint32_t(pix[i]), sample);
-    const Hit h = closest(E, T, o + 3 * i, d + 3 * i, key, uint32_t(bounce));
-    top[i] = prim[i] = inst[i] = rank[i] = -1;
-    t[i] = -1.0f;
+    const emu::Hit h = emu::closest(E, T, o + 3 * i, d + 3 * i, key, uint32_t(bounce));
+    emu::hit_ids(sc, h, top[i], prim[i], t[i]);
+    inst[i] = rank[i] = -1;
     if (h.kh != 0u) {
-      hit_ids(sc, int(h.kh >> 28), int(h.kh & 0x0FFFFFFFu), h.refpos, top[i], prim[i]);
-      t[i] = h.t;
       inst[i] = h.inst;
       rank[i] = h.refpos >= 0 ? sc.ref_rank[h.refpos] : -1;
     }
@@ -268,7 +178,7 @@ extern "C" int lift_emu_paths(const rt_scene_desc* desc, const rt_camera_desc* c
 
 // The NEE shadow rays of n paths at bounce `bounce` and what becomes of them:
 // k_extend's hit (unmerged: shade_path merges the lifted primitives itself),
-// shade_path in the variant run_variant picks (the lift variant when
+// shade_path in the variant pick_variant names (the lift variant when
 // primitives are lifted: a ray a lifted primitive occludes is cleared there),
 // then k_shadow for every ray the job still carries.  vis[i]: bit 0 / 1 the
 // area / HDRI ray is unoccluded; traced[i]: the rays k_shadow walked.
@@ -277,9 +187,7 @@ extern "C" int lift_emu_nee(const rt_scene_desc* desc, const rt_camera_desc* cam
                             const float* d, int n, int32_t* vis, int32_t* traced) {
   emu::EmuScene E;
   if (int rc = load(desc, cam, tlas_builder, node_format, lift, E)) return rc;
-  const DScene& sc = E.d;
-  const bool envis = sc.env.valid && sc.env.use_is && sc.num_lights > 0;   // run_variant
-  emu::TraceArgs T(E.max_depth, int(sc.stack_needed));
+  emu::TraceArgs T(E.max_depth, int(E.d.stack_needed));
   std::vector<uint32_t> spill_sh(T.spill.size() + 1, 0u);
   T.a.spill_sh = spill_sh.data();
   const uint32_t bn = uint32_t(bounce);
@@ -287,15 +195,11 @@ extern "C" int lift_emu_nee(const rt_scene_desc* desc, const rt_camera_desc* cam
     const uint32_t key = path_key(seed, uint32_t(pix[i]), sample);
     const V3 ro = mk(o[3 * i], o[3 * i + 1], o[3 * i + 2]), rd = mk(d[3 * i], d[3 * i + 1], d[3 * i + 2]);
     const float4 h = emu::trace_path(E, T, o + 3 * i, d + 3 * i, key, bn);
-    NeeOut r;
-    if (envis) r = bounce == 0 ? shade_by_kind<true, true>(sc, E, T, h, ro, rd, key, dleft, bn)
-                               : shade_by_kind<true, false>(sc, E, T, h, ro, rd, key, dleft, bn);
-    else r = bounce == 0 ? shade_by_kind<false, true>(sc, E, T, h, ro, rd, key, dleft, bn)
-                         : shade_by_kind<false, false>(sc, E, T, h, ro, rd, key, dleft, bn);
+    const emu::Shaded r = emu::shade_by_kind(E, T, h, ro, rd, mk(1.0f, 1.0f, 1.0f), key, dleft, bn, true);
     const float P[3] = {r.P.x, r.P.y, r.P.z}, da[3] = {r.da.x, r.da.y, r.da.z}, dh[3] = {r.dh.x, r.dh.y, r.dh.z};
     uint32_t v = 0;
-    if ((r.flags & 2u) && shadow(E, T, P, dh, std::numeric_limits<float>::infinity(), key, bn)) v |= 2u;
-    if ((r.flags & 1u) && shadow(E, T, P, da, r.tmax_a, key, bn)) v |= 1u;
+    if ((r.flags & 2u) && (emu::shadow_path(E, T, P, dh, std::numeric_limits<float>::infinity(), key, bn) & 1u)) v |= 2u;
+    if ((r.flags & 1u) && (emu::shadow_path(E, T, P, da, r.tmax_a, key, bn) & 1u)) v |= 1u;
     vis[i] = int32_t(v);
     traced[i] = int32_t(r.flags & 3u);
   }
@@ -334,12 +238,13 @@ int main(int argc, char** argv) {
         float time;
         get_ray(E[0].cam, p % W, p / W, key, ro, rd, time);
         const float o[3] = {ro.x, ro.y, ro.z}, d[3] = {rd.x, rd.y, rd.z};
-        const Hit a = closest(E[0], T0, o, d, key, 0u), b = closest(E[1], T1, o, d, key, 0u);
-        int32_t ta = -1, pa = -1, tb = -1, pb = -1;
-        if (a.kh) hit_ids(E[0].d, int(a.kh >> 28), int(a.kh & 0x0FFFFFFFu), a.refpos, ta, pa);
-        if (b.kh) hit_ids(E[1].d, int(b.kh >> 28), int(b.kh & 0x0FFFFFFFu), b.refpos, tb, pb);
+        const emu::Hit a = emu::closest(E[0], T0, o, d, key, 0u), b = emu::closest(E[1], T1, o, d, key, 0u);
+        int32_t ta, pa, tb, pb;
+        float fa, fb;
+        emu::hit_ids(E[0].d, a, ta, pa, fa);
+        emu::hit_ids(E[1].d, b, tb, pb, fb);
         hits += a.kh != 0u;
-        if (ta != tb || pa != pb || (a.kh && memcmp(&a.t, &b.t, 4) != 0)) ++diff;
+        if (ta != tb || pa != pb || memcmp(&fa, &fb, 4) != 0) ++diff;
       }
       printf("{\"tlas\": %d, \"format\": %d, \"format_used\": %d, \"lifted\": %d, \"rays\": %d, \"hits\": %d, \"differ\": %d}\n",
              tlas, fmt, format_of(E[1].d), E[1].d.num_prim_recs, W * Hh, hits, diff);

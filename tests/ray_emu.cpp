@@ -22,14 +22,14 @@ int main(int argc, char** argv) {
   emu::EmuScene E;
   if (int rc = emu::load(argv[1], atoi(argv[2]), argv[3], E)) return rc;
   const DScene& d = E.d;
-  if (d.has_volumes || d.n_circles > 0 || d.dfs_order) {
+  if (pick_variant(d).vol) {
     fprintf(stderr, "ray_emu: rare-primitive scenes are not supported\n");
     return 3;
   }
   emu::TraceArgs T(E.max_depth, int(E.d.stack_needed));
   float o[3], dd[3];
   while (scanf("%f %f %f %f %f %f", &o[0], &o[1], &o[2], &dd[0], &dd[1], &dd[2]) == 6) {
-    const float4 h = emu::trace_one(E, T, o, dd);
+    const float4 h = emu::trace_path(E, T, o, dd);
     uint32_t w[4];
     memcpy(w, &h, 16);
     printf("%u %u %.9g %d %d\n", w[1] >> 28, w[1] & 0x0FFFFFFFu, double(h.x), int(w[2]), int(w[3]));

@@ -84,15 +84,28 @@ def test_flattened_indices_in_range(probe, name, collapse):
 @pytest.mark.parametrize("name,batch", [("simple", 0), ("cornell", 1), ("cornell-smoke", 0), ("cornell-lucy", 1),
                                         ("hdri-nee", 0), ("hdri-test", 1), ("random", 0), ("primitives", 1),
                                         ("perlin", 0), ("earth", 0), ("glossy-metal", 0), ("cornell-glossy", 1),
-                                        ("quads", 0), ("checkered-spheres", 0), ("cornell-rotations", 1)])
+                                        ("quads", 0), ("checkered-spheres", 0), ("cornell-rotations", 1),
+                                        ("cornell+lift", 0), ("cornell-lucy+lift", 1)])
 def test_wavefront_kernels_under_asan_match_oracle(wave, O, g, tmp_path, name, batch):
+    """NAME+lift: flattened with the world quads / spheres lifted out of the
+    world BVH (RTG_EMU_LIFT=1, what contexts do by default; cornell-lucy
+    lifts its six walls, cornell shades in the volume variant and lifts
+    nothing): with fp32 nodes every ray is decided as in the unlifted scene,
+    so the same oracle bar holds."""
     spp, seed, width = 2, 77, 40
+    env = _env()
+    lifted = 0
+    if name.endswith("+lift"):
+        name = name[:-len("+lift")]
+        env["RTG_EMU_LIFT"] = "1"
+        lifted = 6 if name == "cornell-lucy" else 0
     out = tmp_path / f"{name}.f32"
     args = [wave, name, str(width), str(spp), str(seed), ASSETS, str(out)]
     if batch:
         args.append(str(batch))   # one sample per batch: several batches
-    r = subprocess.run(args, capture_output=True, text=True, env=_env(), timeout=600)
+    r = subprocess.run(args, capture_output=True, text=True, env=env, timeout=600)
     assert r.returncode == 0, (r.stdout + r.stderr)[-4000:]
+    assert json.loads(r.stdout.strip().splitlines()[-1])["lifted"] == lifted
     if name in ("hdri-test", "hdri-nee"):   # the HDR asset's texels in their 4-B RGBE form (DEnv::rgbe)
         assert json.loads(r.stdout.strip().splitlines()[-1])["rgbe"] == 1
     kw = dict(width=width)

@@ -34,12 +34,13 @@ int main(int argc, char** argv) {
   // the pipeline itself, its buffers and its kernel variants: wave_run.h
   std::vector<float> out;
   size_t S = 0;
-  const int err = wave_run::render(E, seed, 0u, spp, spb, E.max_depth, d.env.valid && d.env.use_is, out, &S);
+  const int err = wave_run::render(E, seed, 0u, spp, spb, E.max_depth, out, &S);
   FILE* f = fopen(argv[6], "wb");
   if (!f) return 5;
   fwrite(out.data(), sizeof(float), out.size(), f);
   fclose(f);
-  printf("{\"width\": %d, \"height\": %d, \"slots\": %zu, \"overflow\": %d, \"wide\": %d, \"nodes8\": %zu, \"rgbe\": %d}\n",
-         cam.width, cam.height, S, err, d.wide_nodes, E.h.nodes8.size(), d.env.rgbe != nullptr ? 1 : 0);
+  printf("{\"width\": %d, \"height\": %d, \"slots\": %zu, \"overflow\": %d, \"wide\": %d, \"nodes8\": %zu, \"rgbe\": %d, "
+         "\"lifted\": %d}\n",
+         cam.width, cam.height, S, err, d.wide_nodes, E.h.nodes8.size(), d.env.rgbe != nullptr ? 1 : 0, d.num_prim_recs);
   return err ? 6 : 0;
 }

@@ -6,7 +6,8 @@
 // scene under AddressSanitizer + UBSan; tests/hits_emu.cpp (hits_emu_render)
 // over a caller's description as a plain library.  The traversal stack ring
 // is 4 entries so deep traversals take the spill path.  Include after
-// wavefront.hip, wave_layout.h and emu_scene.h.  Not a product path.
+// wavefront.hip (which brings wave_variant.h), wave_layout.h and emu_scene.h.
+// Not a product path.
 #pragma once
 #include <cstdint>
 #include <cstdlib>
@@ -76,11 +77,11 @@ void run(const DScene& sc, const DCamera& cam, WaveArgs a, uint32_t spp, uint32_
 
 // One frame of the flattened scene E: spp samples from sample_offset in
 // batches of spb, to depth max_depth, into out (H * W * 3 sums, the buffer
-// rt_render returns).  envis: whether the importance-sampled HDRI variant of
-// the kernels runs (the caller's rule).  Returns the kernels' error flag;
-// *slots: the path slots of a batch.
+// rt_render returns), through the kernel variants the product picks for the
+// scene (wave_variant.h).  Returns the kernels' error flag; *slots: the path
+// slots of a batch.
 inline int render(const emu::EmuScene& E, uint32_t seed, uint32_t sample_offset, uint32_t spp, uint32_t spb, int max_depth,
-                  bool envis, std::vector<float>& out, size_t* slots) {
+                  std::vector<float>& out, size_t* slots) {
   const DScene& d = E.d;
   const DCamera& cam = E.cam;
   const uint32_t npix = uint32_t(cam.width) * uint32_t(cam.height);
@@ -132,29 +133,13 @@ inline int render(const emu::EmuScene& E, uint32_t seed, uint32_t sample_offset,
   a.out_pixels = uint32_t(npix);
 
   out.assign(size_t(npix) * 3, 0.0f);
-  const bool vol = d.has_volumes != 0 || d.n_circles > 0 || d.dfs_order != 0;
-#define RUNQ(V, H, F)                                                  \
-  do {                                                                 \
-    if constexpr (!(V)) {                                              \
-      if (d.wide_nodes) { run<V, H, F, false, true>(d, cam, a, spp, spb, max_depth, out.data(), sample_offset); break; } \
-    }                                                                  \
-    if (d.quant_nodes) run<V, H, F, true>(d, cam, a, spp, spb, max_depth, out.data(), sample_offset); \
-    else run<V, H, F, false>(d, cam, a, spp, spb, max_depth, out.data(), sample_offset); \
-  } while (0)
-#define RUN(V, H)                                                      \
-  do {                                                                 \
-    if (d.shade_kind == SHADE_FULL) RUNQ(V, H, SHADE_FULL);            \
-    else if (d.shade_kind == SHADE_VOL) RUNQ(V, H, SHADE_VOL);         \
-    else if (d.shade_kind == SHADE_MAT) RUNQ(V, H, SHADE_MAT);         \
-    else RUNQ(V, H, SHADE_LEAN);                                       \
-  } while (0)
-  if (vol) {
-    if (envis) RUN(true, true); else RUN(true, false);
-  } else {
-    if (envis) RUN(false, true); else RUN(false, false);
-  }
-#undef RUNQ
-#undef RUN
+  const WaveVariant v = pick_variant(d);
+  with_traversal(v, [&](auto V, auto Q, auto W) {
+    with_shading(v, [&](auto H, auto F) {
+      run<decltype(V)::value, decltype(H)::value, decltype(F)::value, decltype(Q)::value, decltype(W)::value>(
+          d, cam, a, spp, spb, max_depth, out.data(), sample_offset);
+    });
+  });
   return err;
 }
 
