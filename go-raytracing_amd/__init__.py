@@ -142,6 +142,39 @@ class RtAdaptiveStats(C.Structure):
                 ("pixels_at_max", C.c_int32)]
 
 
+class RtRay(C.Structure):
+    """rt_ray (32 B): origin, tmin, direction, tmax."""
+    _fields_ = [("o", C.c_float * 3), ("tmin", C.c_float), ("d", C.c_float * 3), ("tmax", C.c_float)]
+
+
+class RtRayHit(C.Structure):
+    """rt_ray_hit (32 B): t, top, prim, material, normal, flags."""
+    _fields_ = [("t", C.c_float), ("top", C.c_int32), ("prim", C.c_int32), ("material", C.c_int32),
+                ("n", C.c_float * 3), ("flags", C.c_uint32)]
+
+
+RT_HIT_FRONT = 1
+RT_HIT_INVALID_RAY = 2
+# numpy views of arrays of the two structs
+RAY_DTYPE = np.dtype([("o", np.float32, 3), ("tmin", np.float32), ("d", np.float32, 3), ("tmax", np.float32)])
+RAY_HIT_DTYPE = np.dtype([("t", np.float32), ("top", np.int32), ("prim", np.int32), ("material", np.int32),
+                          ("n", np.float32, 3), ("flags", np.uint32)])
+
+
+def make_rays(o, d, tmin=0.001, tmax=float("inf")) -> np.ndarray:
+    """An array of rt_ray (RAY_DTYPE) from origins and directions (n, 3) and
+    per-ray or scalar tmin / tmax."""
+    o = np.asarray(o, np.float32).reshape(-1, 3)
+    d = np.asarray(d, np.float32).reshape(-1, 3)
+    if o.shape != d.shape:
+        raise ValueError("origins and directions differ in shape")
+    rays = np.zeros(o.shape[0], RAY_DTYPE)
+    rays["o"], rays["d"] = o, d
+    rays["tmin"] = np.broadcast_to(np.asarray(tmin, np.float32), (o.shape[0],))
+    rays["tmax"] = np.broadcast_to(np.asarray(tmax, np.float32), (o.shape[0],))
+    return rays
+
+
 class RtWorkCounts(C.Structure):
     _fields_ = [(n, C.c_uint64) for n in ("samples", "rays", "shadow_rays", "node_visits", "sphere_tests",
                                           "quad_tests", "tri_tests", "plane_tests", "instance_visits",
@@ -265,6 +298,11 @@ def rtgpu() -> C.CDLL:
             lib.rt_normalize_samples.argtypes = [P, C.POINTER(C.c_float), I32, U32P, I32, I32, I32,
                                                  C.POINTER(C.c_float)]
             lib.rt_normalize_samples_device.argtypes = [P, P, I32, P, I32, I32, I32, P, P]
+        if hasattr(lib, "rt_trace_rays"):
+            lib.rt_trace_rays.argtypes = [P, C.POINTER(RtRay), C.c_int64, C.c_float, C.POINTER(RtRayHit)]
+            lib.rt_trace_rays_device.argtypes = [P, P, C.c_int64, C.c_float, P, P]
+            lib.rt_occluded.argtypes = [P, C.POINTER(RtRay), C.c_int64, C.c_float, C.POINTER(C.c_uint8)]
+            lib.rt_occluded_device.argtypes = [P, P, C.c_int64, C.c_float, P, P]
         _rtgpu = lib
     return _rtgpu
 
@@ -886,6 +924,44 @@ class Context:
         nee = np.zeros(n, np.int32)
         self._check(self._lib.rt_shadow_visibility(self._h, C.byref(camera), seed, sample, bounce, _i32p(nee)))
         return nee
+
+    # ---- ray queries (rt_trace_rays / rt_occluded)
+    def trace_rays_raw(self, rays: np.ndarray, time: float = 0.0) -> np.ndarray:
+        """rt_trace_rays over an array of rt_ray (RAY_DTYPE): the rt_ray_hit
+        records (RAY_HIT_DTYPE)."""
+        rays = np.ascontiguousarray(rays, RAY_DTYPE)
+        hits = np.zeros(rays.shape[0], RAY_HIT_DTYPE)
+        self._check(self._lib.rt_trace_rays(self._h, rays.ctypes.data_as(C.POINTER(RtRay)), rays.shape[0], time,
+                                            hits.ctypes.data_as(C.POINTER(RtRayHit))))
+        return hits
+
+    def trace_rays(self, o, d, tmin=0.001, tmax=float("inf"), time: float = 0.0):
+        """Closest hit of every ray o + t d over (tmin, tmax) in the uploaded
+        scene (rt_trace_rays): (top, prim, t, material, n, flags); a miss has
+        ids -1, t -1, n 0; flags: RT_HIT_FRONT, RT_HIT_INVALID_RAY."""
+        h = self.trace_rays_raw(make_rays(o, d, tmin, tmax), time)
+        return (h["top"].copy(), h["prim"].copy(), h["t"].copy(), h["material"].copy(), h["n"].copy(),
+                h["flags"].copy())
+
+    def occluded(self, o, d, tmin=0.001, tmax=float("inf"), time: float = 0.0) -> np.ndarray:
+        """1 where anything is hit in the interval, else 0 (rt_occluded, the
+        shadow rays' any-hit rule)."""
+        rays = make_rays(o, d, tmin, tmax)
+        occ = np.zeros(rays.shape[0], np.uint8)
+        self._check(self._lib.rt_occluded(self._h, rays.ctypes.data_as(C.POINTER(RtRay)), rays.shape[0], time,
+                                          occ.ctypes.data_as(C.POINTER(C.c_uint8))))
+        return occ
+
+    def trace_rays_device(self, rays_ptr: int, n: int, hits_ptr: int, time: float = 0.0, stream: int = 0):
+        """rt_trace_rays_device: n rt_ray at device address rays_ptr -> n
+        rt_ray_hit at hits_ptr, asynchronous on `stream`."""
+        self._check(self._lib.rt_trace_rays_device(self._h, C.c_void_p(rays_ptr), n, time, C.c_void_p(hits_ptr),
+                                                   C.c_void_p(stream)))
+
+    def occluded_device(self, rays_ptr: int, n: int, occluded_ptr: int, time: float = 0.0, stream: int = 0):
+        """rt_occluded_device: n rt_ray at rays_ptr -> n bytes at occluded_ptr."""
+        self._check(self._lib.rt_occluded_device(self._h, C.c_void_p(rays_ptr), n, time, C.c_void_p(occluded_ptr),
+                                                 C.c_void_p(stream)))
 
 
 # ---------------------------------------------------------------------------

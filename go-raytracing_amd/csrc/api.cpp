@@ -21,6 +21,7 @@
 #include "build.h"
 #include "flatten.h"
 #include "probe.h"
+#include "query.h"
 #include "wavefront.h"
 #include "wave_layout.h"
 #include "denoise.h"
@@ -125,6 +126,15 @@ struct rt_ctx {
   hipEvent_t dyn_ev0 = nullptr;   // start of this device's runs in a dynamic render
   bool dyn_span = false;          // the last render was dynamic: its kernel span starts at dyn_ev0
   int32_t dealt_tiles = 0, dealt_runs = 0;   // this device's share of the last multi-device render
+  // ray queries (rt_trace_rays / rt_occluded, query.hip): the host variants'
+  // staging copies of the rays and the results, and the traversal-stack
+  // spill area of the query grid (grown on demand); q_ev follows the latest
+  // query launch on q_st, so a query on another stream starts after it (they
+  // share the spill area)
+  DevBuf q_rays, q_out, q_spill;
+  hipEvent_t q_ev = nullptr;
+  hipStream_t q_st = nullptr;
+  bool q_pending = false;
 };
 
 namespace {
@@ -847,6 +857,8 @@ void rt_ctx_destroy(rt_ctx* ctx) {
   free_buf(ctx->ad_work); free_buf(ctx->ad_counts);
   if (ctx->ad_pinned) (void)hipHostFree(ctx->ad_pinned);
   free_buf(ctx->frame); free_buf(ctx->frame_rgba); free_buf(ctx->frame_buckets);
+  free_buf(ctx->q_rays); free_buf(ctx->q_out); free_buf(ctx->q_spill);
+  if (ctx->q_ev) (void)hipEventDestroy(ctx->q_ev);
   if (ctx->pix_pinned) (void)hipHostFree(ctx->pix_pinned);
   if (ctx->probe_pinned) (void)hipHostFree(ctx->probe_pinned);
   (void)hipEventDestroy(ctx->pix_ev);
@@ -2068,6 +2080,120 @@ int rt_shadow_visibility(rt_ctx* ctx, const rt_camera_desc* cam, uint32_t seed, 
 int rt_extend_first_hits(rt_ctx* ctx, const rt_camera_desc* cam, uint32_t seed, int32_t sample, int32_t* out_top,
                          int32_t* out_prim, float* out_t) {
   return rt_extend_hits(ctx, cam, seed, sample, 0, out_top, out_prim, out_t, nullptr);
+}
+
+}  // extern "C"
+
+// ---- ray queries (query.hip): closest hit and occlusion for the caller's rays
+namespace {
+
+constexpr int64_t kQueryStageRays = int64_t(1) << 22;   // rays per staging pass of the host variants (128 MiB)
+
+int query_check(rt_ctx* ctx, const void* rays, int64_t n, const void* out) {
+  if (!ctx || !rays || !out || n < 0) return RT_ERR_INVALID;
+  return RT_OK;
+}
+
+// The refusals of every query, before anything is allocated or launched.
+int query_refuse(rt_ctx* ctx, float time) {
+  if (!ctx->has_scene) return set_err(ctx, RT_ERR_NO_SCENE, "no scene uploaded");
+  if (ctx->dscene.n_volumes > 0)
+    return set_err(ctx, RT_ERR_UNSUPPORTED, "ray queries on a scene with volumes are not supported (Volume.Hit needs a path key)");
+  if (!std::isfinite(time)) return set_err(ctx, RT_ERR_INVALID, "ray time is not finite");
+  return RT_OK;
+}
+
+// n > 0 device rays -> n device results on `st`, in launches of at most
+// kQueryMaxRays rays.  The spill area is the context's: a query on another
+// stream than the latest one's first waits for that one.
+int query_device(rt_ctx* ctx, bool any, const rt_ray* rays, int64_t n, float time, void* out, hipStream_t st) {
+  const WaveKnobs knobs = resolve_knobs(ctx->wopt, false);
+  const int cap = spill_cap_for(int(ctx->dscene.stack_needed), kLdsStack);
+  const uint32_t first = uint32_t(std::min<int64_t>(n, int64_t(kQueryMaxRays)));
+  const int blocks = query_blocks(ctx->dscene, any, first, ctx->num_cus, knobs.max_blocks);
+  const size_t lanes = size_t(blocks) * 256u;
+  if (ctx->q_pending && ctx->q_st != st) HIPCHK(hipStreamWaitEvent(st, ctx->q_ev, 0));
+  int rc = ensure(ctx, ctx->q_spill, lanes * size_t(cap) * sizeof(uint32_t));
+  if (rc) return rc;
+  if (!ctx->q_ev) HIPCHK(hipEventCreateWithFlags(&ctx->q_ev, hipEventDisableTiming));
+  for (int64_t off = 0; off < n; off += int64_t(kQueryMaxRays)) {
+    QueryArgs a{};
+    a.rays = reinterpret_cast<const float4*>(rays + off);
+    a.out = any ? static_cast<void*>(static_cast<uint8_t*>(out) + off)
+                : static_cast<void*>(static_cast<rt_ray_hit*>(out) + off);
+    a.n = uint32_t(std::min<int64_t>(n - off, int64_t(kQueryMaxRays)));
+    a.time = time;
+    a.spill = static_cast<uint32_t*>(ctx->q_spill.p);
+    a.spill_lanes = uint32_t(lanes);
+    a.spill_cap = cap;
+    a.err = static_cast<int*>(ctx->errflag.p);
+    // (a shorter last launch never needs more blocks than the first)
+    HIPCHK(launch_query(ctx->dscene, any, a, std::min(blocks, int((a.n + 255u) / 256u)), st));
+  }
+  HIPCHK(hipEventRecord(ctx->q_ev, st));
+  ctx->q_st = st;
+  ctx->q_pending = true;
+  // the error flag follows the query to the host as it follows a render
+  HIPCHK(hipMemcpyAsync(ctx->err_pinned, ctx->errflag.p, sizeof(int), hipMemcpyDeviceToHost, st));
+  HIPCHK(hipEventRecord(ctx->err_ev, st));
+  ctx->err_pending = true;
+  return RT_OK;
+}
+
+// The host variants: staged through the context's buffers, at most
+// kQueryStageRays rays at a time; blocks.
+int query_host(rt_ctx* ctx, bool any, const rt_ray* rays, int64_t n, float time, void* out) {
+  HIPCHK(hipSetDevice(ctx->device));
+  int rc = check_render_error(ctx, true);
+  if (rc || (rc = query_refuse(ctx, time)) || n == 0) return rc;
+  const size_t out_sz = any ? sizeof(uint8_t) : sizeof(rt_ray_hit);
+  const int64_t stage = std::min<int64_t>(n, kQueryStageRays);
+  if ((rc = ensure(ctx, ctx->q_rays, size_t(stage) * sizeof(rt_ray)))) return rc;
+  if ((rc = ensure(ctx, ctx->q_out, size_t(stage) * out_sz))) return rc;
+  for (int64_t off = 0; off < n; off += stage) {
+    const int64_t m = std::min<int64_t>(stage, n - off);
+    HIPCHK(hipMemcpyAsync(ctx->q_rays.p, rays + off, size_t(m) * sizeof(rt_ray), hipMemcpyHostToDevice, ctx->stream));
+    if ((rc = query_device(ctx, any, static_cast<const rt_ray*>(ctx->q_rays.p), m, time, ctx->q_out.p, ctx->stream))) return rc;
+    HIPCHK(hipMemcpyAsync(static_cast<char*>(out) + size_t(off) * out_sz, ctx->q_out.p, size_t(m) * out_sz,
+                          hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+  }
+  return check_render_error(ctx, true);
+}
+
+int query_async(rt_ctx* ctx, bool any, const rt_ray* rays, int64_t n, float time, void* out, void* hip_stream) {
+  HIPCHK(hipSetDevice(ctx->device));
+  hipStream_t st = hip_stream ? static_cast<hipStream_t>(hip_stream) : ctx->stream;
+  // an earlier call's device error surfaces here at the latest, as in rt_render_device
+  int rc = check_render_error(ctx, false);
+  if (rc || (rc = query_refuse(ctx, time)) || n == 0) return rc;
+  return query_device(ctx, any, rays, n, time, out, st);
+}
+
+}  // namespace
+
+extern "C" {
+
+static_assert(sizeof(rt_ray) == 32 && sizeof(rt_ray_hit) == 32, "rt_ray / rt_ray_hit are two 16-B vectors each");
+
+int rt_trace_rays(rt_ctx* ctx, const rt_ray* rays, int64_t n, float time, rt_ray_hit* hits) {
+  if (int rc = query_check(ctx, rays, n, hits)) return rc;
+  return query_host(ctx, false, rays, n, time, hits);
+}
+
+int rt_trace_rays_device(rt_ctx* ctx, const rt_ray* rays_dev, int64_t n, float time, rt_ray_hit* hits_dev, void* hip_stream) {
+  if (int rc = query_check(ctx, rays_dev, n, hits_dev)) return rc;
+  return query_async(ctx, false, rays_dev, n, time, hits_dev, hip_stream);
+}
+
+int rt_occluded(rt_ctx* ctx, const rt_ray* rays, int64_t n, float time, uint8_t* occluded) {
+  if (int rc = query_check(ctx, rays, n, occluded)) return rc;
+  return query_host(ctx, true, rays, n, time, occluded);
+}
+
+int rt_occluded_device(rt_ctx* ctx, const rt_ray* rays_dev, int64_t n, float time, uint8_t* occluded_dev, void* hip_stream) {
+  if (int rc = query_check(ctx, rays_dev, n, occluded_dev)) return rc;
+  return query_async(ctx, true, rays_dev, n, time, occluded_dev, hip_stream);
 }
 
 }  // extern "C"

@@ -12,6 +12,7 @@
 #include <stdint.h>
 #include "dev_layout.h"
 #include "device_common.h"
+#include "hit_ids.h"
 #include "probe.h"
 
 namespace rtg {
@@ -35,17 +36,6 @@ __global__ void tonemap_kernel(const float* accum, int n, int spp, uint8_t* rgba
   }
   o[3] = 255;
   reinterpret_cast<uchar4*>(rgba)[i] = make_uchar4(o[0], o[1], o[2], o[3]);
-}
-
-// Hittable ids of a closest hit (kind, primitive index, TLAS ref position).
-__device__ __forceinline__ void hit_ids(const DScene& sc, int kind, int idx, int refpos, int& top, int& prim) {
-  if (kind == PK_PLANE) { top = prim = sc.plane_hidx[idx]; return; }
-  top = sc.tlas_ref_top[refpos];
-  if (kind == PK_SPHERE) prim = sc.sphere_hidx[idx];
-  else if (kind == PK_QUAD) prim = sc.quad_hidx[idx];
-  else if (kind == PK_TRI) prim = sc.tri_hidx[idx];
-  else if (kind == PK_CIRCLE) prim = sc.circle_hidx[idx];
-  else prim = sc.volume_hidx[idx];
 }
 
 // rt_render_rgba8: the same quantisation for the pixels of a bucket list only

@@ -789,8 +789,75 @@ func (c *Ctx) NormalizeSamples(sums []float32, channels int, counts []uint32, wi
 		(*C.float)(unsafe.Pointer(&out[0]))))
 }
 
+// Ray mirrors rt_ray: the ray O + t D over the interval (TMin, TMax).
+//
+//rtgpu:mirror rt_ray
+type Ray struct {
+	O    [3]float32 `c:"o"`
+	TMin float32    `c:"tmin"`
+	D    [3]float32 `c:"d"`
+	TMax float32    `c:"tmax"`
+}
+
+// RayHit mirrors rt_ray_hit.  A miss has T = -1, Top = Prim = Material = -1,
+// N = 0 and Flags = 0.
+//
+//rtgpu:mirror rt_ray_hit
+type RayHit struct {
+	T        float32    `c:"t"`
+	Top      int32      `c:"top"`
+	Prim     int32      `c:"prim"`
+	Material int32      `c:"material"`
+	N        [3]float32 `c:"n"`
+	Flags    uint32     `c:"flags"`
+}
+
+// RayHit.Flags bits.
+const (
+	HitFront      = 1 // RT_HIT_FRONT
+	HitInvalidRay = 2 // RT_HIT_INVALID_RAY
+)
+
+// Hit reports whether the record is a hit.
+func (h *RayHit) Hit() bool { return h.Prim >= 0 }
+
+// TraceRays finds the closest hit of every ray in the uploaded scene
+// (rt_trace_rays): what world.Hit(ray, Interval{TMin, TMax}) returns, decided
+// as the render's closest-hit kernel decides it.  D need not be unit; T is
+// the ray parameter.  time is the rays' ray.Time() (moving spheres).  A ray
+// with a non-finite or zero component set, or TMax < TMin, comes back as a
+// miss with HitInvalidRay.  Scenes holding a Volume are refused
+// (IsUnsupported).  Blocks.
+func (c *Ctx) TraceRays(rays []Ray, time float32, hits []RayHit) error {
+	if len(hits) < len(rays) {
+		return &Error{StatusInvalid, "hit buffer too small"}
+	}
+	if len(rays) == 0 {
+		return nil
+	}
+	return c.check(C.rt_trace_rays(c.p, (*C.rt_ray)(unsafe.Pointer(&rays[0])), C.int64_t(len(rays)), C.float(time),
+		(*C.rt_ray_hit)(unsafe.Pointer(&hits[0]))))
+}
+
+// Occluded writes 1 for every ray that hits anything in its interval and 0
+// for the others (rt_occluded, the rule of the render's shadow rays).  Blocks.
+func (c *Ctx) Occluded(rays []Ray, time float32, occluded []byte) error {
+	if len(occluded) < len(rays) {
+		return &Error{StatusInvalid, "occlusion buffer too small"}
+	}
+	if len(rays) == 0 {
+		return nil
+	}
+	return c.check(C.rt_occluded(c.p, (*C.rt_ray)(unsafe.Pointer(&rays[0])), C.int64_t(len(rays)), C.float(time),
+		(*C.uint8_t)(unsafe.Pointer(&occluded[0]))))
+}
+
 // Layout checks: each mirror is exactly as large as its C struct.
 var (
+	_ [unsafe.Sizeof(Ray{}) - uintptr(C.sizeof_rt_ray)]byte
+	_ [uintptr(C.sizeof_rt_ray) - unsafe.Sizeof(Ray{})]byte
+	_ [unsafe.Sizeof(RayHit{}) - uintptr(C.sizeof_rt_ray_hit)]byte
+	_ [uintptr(C.sizeof_rt_ray_hit) - unsafe.Sizeof(RayHit{})]byte
 	_ [unsafe.Sizeof(AdaptiveParams{}) - uintptr(C.sizeof_rt_adaptive_params)]byte
 	_ [uintptr(C.sizeof_rt_adaptive_params) - unsafe.Sizeof(AdaptiveParams{})]byte
 	_ [unsafe.Sizeof(AdaptiveStats{}) - uintptr(C.sizeof_rt_adaptive_stats)]byte

@@ -784,6 +784,68 @@ int rt_normalize_samples(rt_ctx* ctx, const float* sums, int32_t channels, const
 int rt_normalize_samples_device(rt_ctx* ctx, const float* sums_dev, int32_t channels, const uint32_t* counts_dev,
                                 int32_t width, int32_t height, int32_t target_spp, float* out_dev, void* hip_stream);
 
+/* ---- Ray queries: closest hit and occlusion for the caller's own rays ------
+ * What does this ray hit in the uploaded scene?  (Picking, autofocus, bakes,
+ * a caller's own integrator: INTEGRATION.md.)  Both calls run the render's
+ * own traversal, so their answers are the render's.
+ *
+ * rt_trace_rays: hits[i] is what world.Hit(ray_i, Interval{tmin, tmax})
+ * returns, decided the way the render's closest-hit kernel decides it:
+ *   the closest hit, and among hits at exactly the same t the one the
+ *   reference's left-first traversal reports;
+ *   interval ends as the primitive tests have them: spheres and planes take
+ *   tmin < t (open, Interval.Surrounds), quads, triangles and circles
+ *   tmin <= t (closed, Interval.Contains); the upper end is open for all of
+ *   them, t < tmax;
+ *   d need not be unit: t is the ray parameter (the hit point is o + t d);
+ *   top / prim are the hittable ids in rt_primary_hits' convention, material
+ *   the winning primitive's index into rt_scene_desc.materials;
+ *   n is HitRecord.Normal (face-forwarded against d, and under transform
+ *   wrappers the normal the reference's wrappers hand back), RT_HIT_FRONT is
+ *   HitRecord.FrontFace;
+ *   a miss is t = -1, top = prim = material = -1, n = 0, flags = 0.
+ * A ray with tmin = 0.001f and tmax = +inf gets, bit for bit, the ids and t
+ * the render's k_extend finds for that ray (rt_extend_hits).
+ *
+ * rt_occluded: the any-hit form, the rule of the render's shadow rays:
+ * occluded[i] = 1 when anything is hit in the interval, else 0.  The lower
+ * end is as above; the upper end is closed for quads, triangles and circles
+ * (t <= tmax) and open for spheres and planes (t < tmax).  Keep tmin / tmax
+ * away from exact hit distances if the end matters.
+ *
+ * Planes, circles and the world quads / spheres that the scene upload lifts
+ * out of the BVH (RT_OPT_LIFT_PRIMS) take part in both calls.
+ *
+ * time is the call's ray.Time(): moving spheres are evaluated at it.  A
+ * caller with several times makes several calls.
+ *
+ * A ray with a non-finite origin or direction component, a zero direction, a
+ * NaN tmin or tmax, or tmax < tmin is reported as a miss (not occluded) with
+ * RT_HIT_INVALID_RAY set; it traces nothing and raises no device error.
+ *
+ * The host variants block; they stage the arrays through buffers the context
+ * owns (grown on demand, freed with it).  The _device variants take device
+ * arrays and are asynchronous on `hip_stream` (NULL = the context's stream);
+ * a device error surfaces as for rt_render_device (the next call, rt_sync).
+ * A multi-device context answers queries on its first device.  n may exceed
+ * 2^30: the call then runs several launches.
+ * RT_ERR_INVALID: null pointers, n < 0, a non-finite time.  n == 0 is RT_OK
+ * and launches nothing.  RT_ERR_NO_SCENE as for rt_render.
+ * RT_ERR_UNSUPPORTED: the scene holds an RT_VOLUME.  Volume.Hit draws random
+ * numbers from the path's key and a bare ray has none; a variant that takes
+ * a key per ray is a follow-up.                                             */
+typedef struct rt_ray { float o[3]; float tmin; float d[3]; float tmax; } rt_ray;          /* 32 B */
+typedef struct rt_ray_hit { float t; int32_t top; int32_t prim; int32_t material;
+                            float n[3]; uint32_t flags; } rt_ray_hit;                      /* 32 B */
+enum { RT_HIT_FRONT = 1, RT_HIT_INVALID_RAY = 2 };
+
+int rt_trace_rays(rt_ctx* ctx, const rt_ray* rays, int64_t n, float time, rt_ray_hit* hits);
+int rt_trace_rays_device(rt_ctx* ctx, const rt_ray* rays_dev, int64_t n, float time, rt_ray_hit* hits_dev,
+                         void* hip_stream);
+int rt_occluded(rt_ctx* ctx, const rt_ray* rays, int64_t n, float time, uint8_t* occluded);
+int rt_occluded_device(rt_ctx* ctx, const rt_ray* rays_dev, int64_t n, float time, uint8_t* occluded_dev,
+                       void* hip_stream);
+
 #ifdef __cplusplus
 }
 #endif
