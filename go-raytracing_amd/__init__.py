@@ -175,6 +175,58 @@ def make_rays(o, d, tmin=0.001, tmax=float("inf")) -> np.ndarray:
     return rays
 
 
+class RtPathRay(C.Structure):
+    """rt_path_ray (32 B): origin, id (the RNG key's pixel word), direction, reserved (0)."""
+    _fields_ = [("o", C.c_float * 3), ("id", C.c_uint32), ("d", C.c_float * 3), ("reserved", C.c_uint32)]
+
+
+class RtRayColorParams(C.Structure):
+    _fields_ = [("samples", C.c_int32), ("max_depth", C.c_int32), ("sample_offset", C.c_int32), ("seed", C.c_uint32),
+                ("accumulate", C.c_int32), ("use_sky_gradient", C.c_int32), ("phantom_hdri", C.c_int32),
+                ("camera_max_depth", C.c_int32), ("background", C.c_double * 3)]
+
+
+class RtRayColorStats(C.Structure):
+    _fields_ = [("kernel_ms", C.c_double), ("samples", C.c_uint64), ("invalid_rays", C.c_uint64)]
+
+
+PATH_RAY_DTYPE = np.dtype([("o", np.float32, 3), ("id", np.uint32), ("d", np.float32, 3), ("reserved", np.uint32)])
+
+
+def make_path_rays(o, d, ids=None) -> np.ndarray:
+    """An array of rt_path_ray (PATH_RAY_DTYPE) from origins and directions
+    (n, 3); ids: each ray's RNG key word (default: its index)."""
+    o = np.asarray(o, np.float32).reshape(-1, 3)
+    d = np.asarray(d, np.float32).reshape(-1, 3)
+    if o.shape != d.shape:
+        raise ValueError("origins and directions differ in shape")
+    rays = np.zeros(o.shape[0], PATH_RAY_DTYPE)
+    rays["o"], rays["d"] = o, d
+    rays["id"] = np.arange(o.shape[0], dtype=np.uint32) if ids is None else np.asarray(ids, np.uint32).reshape(-1)
+    return rays
+
+
+def ray_color_params(samples: int, depth: int, seed: int = 1, sample_offset: int = 0, camera=None,
+                     accumulate: bool = False, **sky) -> RtRayColorParams:
+    """rt_ray_color_params.  camera: an RtCameraDesc whose background,
+    use_sky_gradient, phantom_hdri and max_depth (as camera_max_depth) are
+    copied; **sky: any of those four fields by name, overriding the camera's."""
+    p = RtRayColorParams()
+    p.samples, p.max_depth, p.sample_offset, p.seed = samples, depth, sample_offset, seed
+    p.accumulate = 1 if accumulate else 0
+    if camera is not None:
+        p.background = camera.background
+        p.use_sky_gradient, p.phantom_hdri, p.camera_max_depth = camera.use_sky_gradient, camera.phantom_hdri, camera.max_depth
+    for k, v in sky.items():
+        if k == "background":
+            p.background = (C.c_double * 3)(*[float(x) for x in v])
+        elif k in ("use_sky_gradient", "phantom_hdri", "camera_max_depth"):
+            setattr(p, k, int(v))
+        else:
+            raise TypeError(f"unknown rt_ray_color_params field {k!r}")
+    return p
+
+
 class RtWorkCounts(C.Structure):
     _fields_ = [(n, C.c_uint64) for n in ("samples", "rays", "shadow_rays", "node_visits", "sphere_tests",
                                           "quad_tests", "tri_tests", "plane_tests", "instance_visits",
@@ -303,6 +355,10 @@ def rtgpu() -> C.CDLL:
             lib.rt_trace_rays_device.argtypes = [P, P, C.c_int64, C.c_float, P, P]
             lib.rt_occluded.argtypes = [P, C.POINTER(RtRay), C.c_int64, C.c_float, C.POINTER(C.c_uint8)]
             lib.rt_occluded_device.argtypes = [P, P, C.c_int64, C.c_float, P, P]
+        if hasattr(lib, "rt_ray_color"):
+            lib.rt_ray_color.argtypes = [P, C.POINTER(RtPathRay), C.c_int64, C.POINTER(RtRayColorParams),
+                                         C.POINTER(C.c_float), C.POINTER(RtRayColorStats)]
+            lib.rt_ray_color_device.argtypes = [P, P, C.c_int64, C.POINTER(RtRayColorParams), P, P]
         _rtgpu = lib
     return _rtgpu
 
@@ -962,6 +1018,32 @@ class Context:
         """rt_occluded_device: n rt_ray at rays_ptr -> n bytes at occluded_ptr."""
         self._check(self._lib.rt_occluded_device(self._h, C.c_void_p(rays_ptr), n, time, C.c_void_p(occluded_ptr),
                                                  C.c_void_p(stream)))
+
+    # ---- Camera.RayColor for the caller's rays (rt_ray_color)
+    def ray_color(self, rays: np.ndarray, samples: int, depth: int, seed: int = 1, sample_offset: int = 0, camera=None,
+                  accum: Optional[np.ndarray] = None, **sky):
+        """The path integral along the caller's rays (rt_ray_color): rays is an
+        array of rt_path_ray (PATH_RAY_DTYPE, make_path_rays); returns the (n, 3)
+        float32 sums over `samples` paths per ray (divide by the sample count) and
+        the stats.  accum: sums of earlier calls to add to (accumulate).  camera
+        and **sky as ray_color_params."""
+        rays = np.ascontiguousarray(rays, PATH_RAY_DTYPE)
+        n = rays.shape[0]
+        p = ray_color_params(samples, depth, seed, sample_offset, camera, accum is not None, **sky)
+        if accum is None:
+            accum = np.zeros((n, 3), np.float32)
+        if accum.dtype != np.float32 or accum.size != 3 * n or not accum.flags["C_CONTIGUOUS"]:
+            raise ValueError("accum must be a contiguous float32 array of 3 floats per ray")
+        st = RtRayColorStats()
+        self._check(self._lib.rt_ray_color(self._h, rays.ctypes.data_as(C.POINTER(RtPathRay)), n, C.byref(p),
+                                           _f32p(accum), C.byref(st)))
+        return accum, st
+
+    def ray_color_device(self, rays_ptr: int, n: int, params: RtRayColorParams, rgb_ptr: int, stream: int = 0):
+        """rt_ray_color_device: n rt_path_ray at device address rays_ptr -> 3 n
+        floats at rgb_ptr, asynchronous on `stream`."""
+        self._check(self._lib.rt_ray_color_device(self._h, C.c_void_p(rays_ptr), n, C.byref(params),
+                                                  C.c_void_p(rgb_ptr), C.c_void_p(stream)))
 
 
 # ---------------------------------------------------------------------------

@@ -22,6 +22,7 @@
 #include "flatten.h"
 #include "probe.h"
 #include "query.h"
+#include "ray_source.h"
 #include "wavefront.h"
 #include "wave_layout.h"
 #include "denoise.h"
@@ -135,6 +136,13 @@ struct rt_ctx {
   hipEvent_t q_ev = nullptr;
   hipStream_t q_st = nullptr;
   bool q_pending = false;
+  // rt_ray_color's host variant: its staging copies of the rays and the sums;
+  // rc_ev follows the latest call's work on rc_st, so a call on another stream
+  // starts after it (they share the batch buffers)
+  DevBuf rc_rays, rc_rgb;
+  hipEvent_t rc_ev = nullptr;
+  hipStream_t rc_st = nullptr;
+  bool rc_pending = false;
 };
 
 namespace {
@@ -342,6 +350,9 @@ struct RenderRun {
   // the span rt_last_render_kernel_ms reports instead of starting a new one
   bool from_list = false;
   uint32_t list_n = 0;
+  // rt_ray_color (WavePlan::ray_src; with from_list): the list's entries name
+  // rays of `rays`, bounce 0 traces those, and `d_out` holds 3 floats per ray
+  const RaySource* rays = nullptr;
 };
 
 // LDS stack ring (kLdsStack entries per lane) + global spill up to
@@ -510,7 +521,7 @@ int render_wave(rt_ctx* ctx, const DCamera& dc, const rt_render_params* p, const
     a.nee_probe = run.probing ? 1u : 0u;
     a.spill_lanes = spill.lanes;
     a.spill_cap = spill.cap;
-    a.out_pixels = uint32_t(dc.width) * uint32_t(dc.height);
+    a.out_pixels = run.rays ? run.rays->num_rays : uint32_t(dc.width) * uint32_t(dc.height);
     ctx->twin_args[t] = a;
   }
   ctx->num_twins = nt;
@@ -527,6 +538,7 @@ int render_wave(rt_ctx* ctx, const DCamera& dc, const rt_render_params* p, const
     plan.mom_acc = mom_acc;
     plan.mom_out = run.mom_out;
   }
+  plan.ray_src = run.rays;
   plan.num_cus = ctx->num_cus;
   plan.max_blocks = knobs.max_blocks;
   plan.num_twins = nt;
@@ -850,6 +862,7 @@ void rt_ctx_destroy(rt_ctx* ctx) {
   if (ctx->err_ev) (void)hipEventDestroy(ctx->err_ev);
   free_buf(ctx->wstate); free_buf(ctx->wq); free_buf(ctx->wpix); free_buf(ctx->wacc);
   free_buf(ctx->wspill);
+  free_buf(ctx->rc_rays); free_buf(ctx->rc_rgb);
   free_buf(ctx->wfacc); free_buf(ctx->feat);
   free_buf(ctx->dn_work); free_buf(ctx->dn_in); free_buf(ctx->dn_feat); free_buf(ctx->dn_out);
   free_buf(ctx->wmacc); free_buf(ctx->mom);
@@ -859,6 +872,7 @@ void rt_ctx_destroy(rt_ctx* ctx) {
   free_buf(ctx->frame); free_buf(ctx->frame_rgba); free_buf(ctx->frame_buckets);
   free_buf(ctx->q_rays); free_buf(ctx->q_out); free_buf(ctx->q_spill);
   if (ctx->q_ev) (void)hipEventDestroy(ctx->q_ev);
+  if (ctx->rc_ev) (void)hipEventDestroy(ctx->rc_ev);
   if (ctx->pix_pinned) (void)hipHostFree(ctx->pix_pinned);
   if (ctx->probe_pinned) (void)hipHostFree(ctx->probe_pinned);
   (void)hipEventDestroy(ctx->pix_ev);
@@ -2170,6 +2184,73 @@ int query_async(rt_ctx* ctx, bool any, const rt_ray* rays, int64_t n, float time
   return query_device(ctx, any, rays, n, time, out, st);
 }
 
+// ---- rt_ray_color: the render path in its ray mode (ray_source.hip) ---------
+
+constexpr int64_t kRayColorMaxRays = (int64_t(1) << 31) - 1;
+
+// The refusals that need no device, then the DCamera rayColorInternal reads:
+// background, sky, phantom and the depth its test compares with (no geometry).
+int ray_color_check(rt_ctx* ctx, const rt_ray_color_params* p, int64_t n, DCamera& dc) {
+  if (n < 0 || n > kRayColorMaxRays) return set_err(ctx, RT_ERR_INVALID, "ray count outside 0 .. 2^31 - 1");
+  if (p->samples < 1 || p->max_depth < 1 || p->sample_offset < 0 || p->camera_max_depth < 0)
+    return set_err(ctx, RT_ERR_INVALID, "bad samples / depth / offset");
+  for (int a = 0; a < 3; ++a)
+    if (!std::isfinite(p->background[a])) return set_err(ctx, RT_ERR_INVALID, "background is not finite");
+  if (!ctx->has_scene) return set_err(ctx, RT_ERR_NO_SCENE, "no scene uploaded");
+  for (int a = 0; a < 3; ++a) dc.background[a] = float(p->background[a]);
+  dc.use_sky = p->use_sky_gradient ? 1 : 0;
+  dc.phantom = p->phantom_hdri ? 1 : 0;
+  dc.cam_max_depth = p->camera_max_depth ? p->camera_max_depth : p->max_depth;
+  dc.width = dc.height = 1;
+  return RT_OK;
+}
+
+// n > 0 device rays -> n device sums on `st`.  A batch holds at least one
+// sample of every ray of a range, so the array is cut into consecutive ranges
+// of at most the batch's slots; each range is one render over the identity
+// list (ray k of the range -> rgb[3k]), with all its samples, so a ray's sum
+// never depends on the cut.
+int ray_color_device(rt_ctx* ctx, const DCamera& dc, const rt_path_ray* rays, int64_t n, const rt_ray_color_params* p,
+                     float* rgb, hipStream_t st) {
+  const bool lit = ctx->dscene.num_lights > 0;
+  const WaveKnobs knobs = resolve_knobs(ctx->wopt, false);
+  size_t target = knobs.slots;
+  if (target == 0) {
+    size_t free_b = 0, total_b = 0;
+    if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) free_b = size_t(8) << 30;
+    target = auto_target(free_b, ctx->wstate.bytes + ctx->wq.bytes, lit);
+  }
+  const int64_t range = std::max<int64_t>(1, std::min<int64_t>(n, int64_t(std::min(target, kMaxSlots))));
+  if (!ctx->rc_ev) HIPCHK(hipEventCreateWithFlags(&ctx->rc_ev, hipEventDisableTiming));
+  if (ctx->rc_pending && ctx->rc_st != st) HIPCHK(hipStreamWaitEvent(st, ctx->rc_ev, 0));
+  int rc = ensure(ctx, ctx->wpix, size_t(range) * sizeof(uint32_t));
+  if (rc) return rc;
+  HIPCHK(launch_ray_identity(static_cast<uint32_t*>(ctx->wpix.p), uint32_t(range), ctx->num_cus, st));
+  rt_render_params q{};
+  q.samples_per_pixel = p->samples;
+  q.max_depth = p->max_depth;
+  q.sample_offset = p->sample_offset;
+  q.seed = p->seed;
+  q.accumulate = p->accumulate;
+  const std::vector<int4> none;
+  ctx->dyn_span = false;
+  HIPCHK(hipEventRecord(ctx->kev0, st));   // the span covers every range
+  for (int64_t off = 0; off < n; off += range) {
+    RaySource src{};
+    src.rays = reinterpret_cast<const float4*>(rays + off);
+    src.num_rays = uint32_t(std::min<int64_t>(range, n - off));
+    RenderRun run{st};
+    run.from_list = true;
+    run.list_n = src.num_rays;
+    run.rays = &src;
+    if ((rc = render_wave(ctx, dc, &q, none, rgb + 3 * off, run))) return rc;
+  }
+  HIPCHK(hipEventRecord(ctx->rc_ev, st));
+  ctx->rc_st = st;
+  ctx->rc_pending = true;
+  return RT_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -2194,6 +2275,62 @@ int rt_occluded(rt_ctx* ctx, const rt_ray* rays, int64_t n, float time, uint8_t*
 int rt_occluded_device(rt_ctx* ctx, const rt_ray* rays_dev, int64_t n, float time, uint8_t* occluded_dev, void* hip_stream) {
   if (int rc = query_check(ctx, rays_dev, n, occluded_dev)) return rc;
   return query_async(ctx, true, rays_dev, n, time, occluded_dev, hip_stream);
+}
+
+static_assert(sizeof(rt_path_ray) == 32, "rt_path_ray is two 16-B vectors");
+
+int rt_ray_color(rt_ctx* ctx, const rt_path_ray* rays, int64_t n, const rt_ray_color_params* params, float* rgb,
+                 rt_ray_color_stats* stats) {
+  if (!ctx || !rays || !params || !rgb) return RT_ERR_INVALID;
+  HIPCHK(hipSetDevice(ctx->device));
+  DCamera dc{};
+  int rc = ray_color_check(ctx, params, n, dc);
+  if (rc) return rc;
+  uint64_t invalid = 0;
+  for (int64_t i = 0; i < n; ++i) {
+    const rt_path_ray& r = rays[i];
+    if (r.reserved != 0) return set_err(ctx, RT_ERR_INVALID, "a ray's reserved word is not 0");
+    const bool fin = std::isfinite(r.o[0]) && std::isfinite(r.o[1]) && std::isfinite(r.o[2]) && std::isfinite(r.d[0]) &&
+                     std::isfinite(r.d[1]) && std::isfinite(r.d[2]);
+    invalid += !(fin && (r.d[0] != 0.0f || r.d[1] != 0.0f || r.d[2] != 0.0f));   // k_ray_source's guard
+  }
+  if ((rc = check_render_error(ctx, true))) return rc;
+  double ms = 0.0;
+  if (n > 0) {
+    hipStream_t st = ctx->stream;
+    if ((rc = ensure(ctx, ctx->rc_rays, size_t(n) * sizeof(rt_path_ray)))) return rc;
+    if ((rc = ensure(ctx, ctx->rc_rgb, size_t(n) * 3 * sizeof(float)))) return rc;
+    HIPCHK(hipMemcpyAsync(ctx->rc_rays.p, rays, size_t(n) * sizeof(rt_path_ray), hipMemcpyHostToDevice, st));
+    if (params->accumulate)
+      HIPCHK(hipMemcpyAsync(ctx->rc_rgb.p, rgb, size_t(n) * 3 * sizeof(float), hipMemcpyHostToDevice, st));
+    if ((rc = ray_color_device(ctx, dc, static_cast<const rt_path_ray*>(ctx->rc_rays.p), n, params,
+                               static_cast<float*>(ctx->rc_rgb.p), st)))
+      return rc;
+    HIPCHK(hipMemcpyAsync(rgb, ctx->rc_rgb.p, size_t(n) * 3 * sizeof(float), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    if ((rc = check_render_error(ctx, true))) return rc;
+    float f = 0.f;
+    HIPCHK(hipEventElapsedTime(&f, ctx->kev0, ctx->kev1));
+    ms = f;
+  }
+  if (stats) {
+    stats->kernel_ms = ms;
+    stats->samples = uint64_t(n) * uint64_t(params->samples);
+    stats->invalid_rays = invalid;
+  }
+  return RT_OK;
+}
+
+int rt_ray_color_device(rt_ctx* ctx, const rt_path_ray* rays_dev, int64_t n, const rt_ray_color_params* params,
+                        float* rgb_dev, void* hip_stream) {
+  if (!ctx || !rays_dev || !params || !rgb_dev) return RT_ERR_INVALID;
+  HIPCHK(hipSetDevice(ctx->device));
+  hipStream_t st = hip_stream ? static_cast<hipStream_t>(hip_stream) : ctx->stream;
+  DCamera dc{};
+  int rc = ray_color_check(ctx, params, n, dc);
+  // an earlier call's device error surfaces here at the latest, as in rt_render_device
+  if (rc || (rc = check_render_error(ctx, false)) || n == 0) return rc;
+  return ray_color_device(ctx, dc, rays_dev, n, params, rgb_dev, st);
 }
 
 }  // extern "C"

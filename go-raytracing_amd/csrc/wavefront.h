@@ -8,6 +8,8 @@
 
 namespace rtg {
 
+struct RaySource;   // ray_source.h
+
 // Per-bounce path stream: one dense record per live path, indexed by its
 // position in this bounce's stream (SoA of 16-B fields, one dwordx4 per lane
 // per array, so every kernel reads and writes it coalesced).
@@ -133,6 +135,14 @@ struct WavePlan {
   // pixel.  Not with feat_acc or an instrumented run.
   double* const* mom_acc;
   float* mom_out;
+  // Ray mode (rt_ray_color, ray_source.hip): non-null = bounce 0's rays are the
+  // caller's.  Each batch's k_set_counts (stream 0 empty) is followed by
+  // k_ray_source, which writes the valid rays as stream 0 and zeroes Lout, and
+  // bounce 0 runs the later-bounce kernels over that stream (launch_bounce 0);
+  // the twins' "pixel lists" hold ray indices into ray_src->rays, and
+  // launch_wavefront's `out` is the range's 3 floats per ray.  Not with
+  // feat_acc, mom_acc, the path probes or an instrumented run.
+  const RaySource* ray_src;
 };
 
 enum : uint8_t { KC_EXTEND = 0, KC_SHADE = 1, KC_SHADOW = 2, KC_OTHER = 3 };

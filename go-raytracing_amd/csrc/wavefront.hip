@@ -27,6 +27,7 @@
 #include "device_common.h"
 #include "wave_variant.h"
 #include "wavefront.h"
+#include "ray_source.h"
 
 namespace rtg {
 
@@ -1075,6 +1076,10 @@ static hipError_t run_batches(const WaveKernels& k, const DScene& sc, const DCam
   const int nt = plan.num_twins;
   const bool nee = sc.num_lights > 0;
   const size_t shade_lds = shade_lds_bytes(sc);
+  // ray mode (WavePlan::ray_src): bounce 0 reads stream 0 like any later bounce
+  const bool ray = plan.ray_src != nullptr;
+  const ExtendFn extend_first = ray ? k.extend : k.extend0;
+  const ShadeFn shade_first = ray ? k.shade : k.shade0;
   hipError_t e;
   for (uint32_t s0 = 0; s0 < plan.spp; s0 += plan.samples_per_batch) {
     const uint32_t sb = plan.spp - s0 < plan.samples_per_batch ? plan.spp - s0 : plan.samples_per_batch;
@@ -1084,7 +1089,8 @@ static hipError_t run_batches(const WaveKernels& k, const DScene& sc, const DCam
       const WaveArgs& a = as[t];
       const hipStream_t st = sts[t];
       const uint32_t nslots = sb * a.npix;
-      hipLaunchKernelGGL(k_set_counts, dim3(1), dim3(1), 0, st, a.counts, nslots);
+      // (ray mode: stream 0 starts empty and k_ray_source fills it, below)
+      hipLaunchKernelGGL(k_set_counts, dim3(1), dim3(1), 0, st, a.counts, ray ? 0u : nslots);
       if (k.count) hipLaunchKernelGGL(k_count_samples, dim3(1), dim3(1), 0, st, a, nslots);
       // one spill column per resident lane; RT_OPT_MAX_BLOCKS may cap it further
       int max_trav_blocks = int(a.spill_lanes / 256u);
@@ -1093,8 +1099,12 @@ static hipError_t run_batches(const WaveKernels& k, const DScene& sc, const DCam
       gsh[t] = grid_for((const void*)k.shade, 256, shade_lds, nslots, cus);
       gsd[t] = cap(grid_for((const void*)k.shadow, 256, 0, nslots, cus));
       gap[t] = grid_for((const void*)k.nee_apply, 256, 0, nslots, cus);
-      gext0[t] = cap(grid_for((const void*)k.extend0, 256, 0, nslots, cus));
+      gext0[t] = cap(grid_for((const void*)extend_first, 256, 0, nslots, cus));
       gext[t] = cap(grid_for((const void*)k.extend, 256, 0, nslots, cus));
+      if (ray) {
+        if ((e = launch_ray_source(a, *plan.ray_src, nslots, sample_base, cus, st)) != hipSuccess) return e;
+        RTG_LAUNCHED("k_ray_source", 0, st);
+      }
     }
     if (plan.bounces_run) *plan.bounces_run = 0;
     if (plan.feat_acc) {
@@ -1145,16 +1155,16 @@ static hipError_t run_batches(const WaveKernels& k, const DScene& sc, const DCam
         // poison the hit records: k_shade reports any that k_extend did not write
         if ((e = hipMemsetAsync(a.hit, 0xFF, size_t(a.slots) * sizeof(float4), st)) != hipSuccess) return e;
 #endif
-        // bounce 0 regenerates the camera rays (no stream), later bounces read s[c]
+        // bounce 0 regenerates the camera rays (no stream; in ray mode it reads s[0] too), later bounces read s[c]
         if ((e = mark_begin(plan, uint8_t(KC_EXTEND | (t << KC_TWIN_SHIFT)), st)) != hipSuccess) return e;
-        hipLaunchKernelGGL(b == 0 ? k.extend0 : k.extend, dim3(b == 0 ? gext0[t] : gext[t]), dim3(256), 0, st, sc, cam, a,
+        hipLaunchKernelGGL(b == 0 ? extend_first : k.extend, dim3(b == 0 ? gext0[t] : gext[t]), dim3(256), 0, st, sc, cam, a,
                            a.s[c], cnt_stream[c], cnt_stream[nx], cnt_sh, fetch_sh, fetch_ext, sample_base);
         if ((e = mark_end(plan, st)) != hipSuccess) return e;
         RTG_LAUNCHED("k_extend", b, st);
         // k_shade b waits for k_nee_apply b - 1
         if (ovl && b > 0 && (e = hipStreamWaitEvent(st, plan.ev_nee[t], 0)) != hipSuccess) return e;
         if ((e = mark_begin(plan, uint8_t(KC_SHADE | (t << KC_TWIN_SHIFT)), st)) != hipSuccess) return e;
-        hipLaunchKernelGGL(b == 0 ? k.shade0 : k.shade, dim3(gsh[t]), dim3(256), shade_lds, st, sc, cam, a, a.s[c],
+        hipLaunchKernelGGL(b == 0 ? shade_first : k.shade, dim3(gsh[t]), dim3(256), shade_lds, st, sc, cam, a, a.s[c],
                            cnt_stream[c], a.s[nx], cnt_stream[nx], cnt_sh, sample_base, uint32_t(b));
         if ((e = mark_end(plan, st)) != hipSuccess) return e;
         RTG_LAUNCHED("k_shade", b, st);
@@ -1295,6 +1305,7 @@ hipError_t launch_wavefront(const DScene& sc, const DCamera& cam, const WaveArgs
   if (feat && (count || plan.max_depth != 1)) return hipErrorInvalidValue;
   const bool mom = plan.mom_acc != nullptr;     // the frame, and the moments image plan.mom_out (moments.h)
   if (mom && (count || feat || !plan.mom_out)) return hipErrorInvalidValue;
+  if (plan.ray_src && (count || feat || mom)) return hipErrorInvalidValue;   // ray mode: the plain render path only
   for (int t = 0; t < nt; ++t) {
     if (feat) e = hipMemsetAsync(plan.feat_acc[t], 0, size_t(as[t].npix) * kFeatFloats * sizeof(double), sts[t]);
     else e = hipMemsetAsync(as[t].acc, 0, size_t(as[t].npix) * 3 * sizeof(double), sts[t]);

@@ -852,8 +852,74 @@ func (c *Ctx) Occluded(rays []Ray, time float32, occluded []byte) error {
 		(*C.uint8_t)(unsafe.Pointer(&occluded[0]))))
 }
 
+// PathRay mirrors rt_path_ray: the ray O + t D and the pixel word of its RNG
+// key.  ID has nothing to do with where the result is written; rays that
+// share an ID and a sample index follow the same random decisions.  Reserved
+// must be 0.
+//
+//rtgpu:mirror rt_path_ray
+type PathRay struct {
+	O        [3]float32 `c:"o"`
+	ID       uint32     `c:"id"`
+	D        [3]float32 `c:"d"`
+	Reserved uint32     `c:"reserved"`
+}
+
+// RayColorParams mirrors rt_ray_color_params.  Of the Camera only what
+// rayColorInternal reads: Background, UseSkyGradient, and PhantomHDRI with
+// CameraMaxDepth (0 = MaxDepth).
+//
+//rtgpu:mirror rt_ray_color_params
+type RayColorParams struct {
+	Samples        int32      `c:"samples"`
+	MaxDepth       int32      `c:"max_depth"`
+	SampleOffset   int32      `c:"sample_offset"`
+	Seed           uint32     `c:"seed"`
+	Accumulate     int32      `c:"accumulate"`
+	UseSkyGradient int32      `c:"use_sky_gradient"`
+	PhantomHDRI    int32      `c:"phantom_hdri"`
+	CameraMaxDepth int32      `c:"camera_max_depth"`
+	Background     [3]float64 `c:"background"`
+}
+
+// RayColorStats mirrors rt_ray_color_stats.
+//
+//rtgpu:mirror rt_ray_color_stats
+type RayColorStats struct {
+	KernelMs    float64 `c:"kernel_ms"`
+	Samples     uint64  `c:"samples"`
+	InvalidRays uint64  `c:"invalid_rays"`
+}
+
+// RayColor is Camera.RayColor for the caller's rays (rt_ray_color): rgb[3*i..]
+// receives the sum over p.Samples paths of rayColorInternal(rays[i],
+// p.MaxDepth), linear; the caller divides by the sample count.  Sample s of
+// ray i runs under the key (p.Seed, rays[i].ID, p.SampleOffset + s) through
+// the render's own kernels, so scenes holding a Volume are served.  D need not
+// be unit.  A ray with a non-finite component or a zero direction adds
+// nothing and is counted in the stats.  Blocks.
+func (c *Ctx) RayColor(rays []PathRay, p RayColorParams, rgb []float32) (RayColorStats, error) {
+	var st RayColorStats
+	if len(rgb) < 3*len(rays) {
+		return st, &Error{StatusInvalid, "radiance buffer too small"}
+	}
+	if len(rays) == 0 {
+		return st, nil
+	}
+	rc := C.rt_ray_color(c.p, (*C.rt_path_ray)(unsafe.Pointer(&rays[0])), C.int64_t(len(rays)),
+		(*C.rt_ray_color_params)(unsafe.Pointer(&p)), (*C.float)(unsafe.Pointer(&rgb[0])),
+		(*C.rt_ray_color_stats)(unsafe.Pointer(&st)))
+	return st, c.check(rc)
+}
+
 // Layout checks: each mirror is exactly as large as its C struct.
 var (
+	_ [unsafe.Sizeof(PathRay{}) - uintptr(C.sizeof_rt_path_ray)]byte
+	_ [uintptr(C.sizeof_rt_path_ray) - unsafe.Sizeof(PathRay{})]byte
+	_ [unsafe.Sizeof(RayColorParams{}) - uintptr(C.sizeof_rt_ray_color_params)]byte
+	_ [uintptr(C.sizeof_rt_ray_color_params) - unsafe.Sizeof(RayColorParams{})]byte
+	_ [unsafe.Sizeof(RayColorStats{}) - uintptr(C.sizeof_rt_ray_color_stats)]byte
+	_ [uintptr(C.sizeof_rt_ray_color_stats) - unsafe.Sizeof(RayColorStats{})]byte
 	_ [unsafe.Sizeof(Ray{}) - uintptr(C.sizeof_rt_ray)]byte
 	_ [uintptr(C.sizeof_rt_ray) - unsafe.Sizeof(Ray{})]byte
 	_ [unsafe.Sizeof(RayHit{}) - uintptr(C.sizeof_rt_ray_hit)]byte

@@ -846,6 +846,92 @@ int rt_occluded(rt_ctx* ctx, const rt_ray* rays, int64_t n, float time, uint8_t*
 int rt_occluded_device(rt_ctx* ctx, const rt_ray* rays_dev, int64_t n, float time, uint8_t* occluded_dev,
                        void* hip_stream);
 
+/* ---- Camera.RayColor for the caller's rays (camera.go:438-518) -------------
+ * What radiance arrives along this ray?  (Light probes, irradiance and
+ * lightmap bakes, reflection captures, an orthographic, panoramic or fisheye
+ * camera, a caller's own sampling pattern: INTEGRATION.md.)  The path integral
+ * of the render, started at rays the caller supplies instead of at a camera's
+ * pixels.
+ *
+ * Result: rgb[3*i .. 3*i+2] is the sum, over the call's `samples` samples, of
+ * rayColorInternal(ray_i, max_depth): linear radiance, and the caller divides
+ * by the sample count, as for rt_render.  Sample s of ray i runs under the
+ * path key path_key(seed, rays[i].id, sample_offset + s) and goes through
+ * exactly what a render's path goes through from bounce 0 on: the same
+ * kernels, the interval (0.001, +inf), the world quads / spheres the upload
+ * lifts (RT_OPT_LIFT_PRIMS), volumes in either RT_OPT_VOLUMES placement, next
+ * event estimation, the light-hit rule, the clamp, and the long-tail kernel
+ * (RT_OPT_TAIL).  Scenes with an RT_VOLUME are served: a path carries the key
+ * Volume.Hit draws from.
+ *
+ * id is only the RNG key's pixel word; it has nothing to do with where the
+ * result is written (always slot i).  Rays that share an id and a sample index
+ * follow the same random decisions; distinct ids give independent paths.
+ * Give every ray of a bake its own id.
+ *
+ * ray.Time() is the key's camera-domain time draw (camera.go:370), as in a
+ * render, so moving spheres blur over a ray's samples.  There is no per-ray
+ * time, tmin or tmax.  d need not be unit (camera rays are not unit either).
+ *
+ * Of the Camera the call reads only what rayColorInternal reads: background,
+ * use_sky_gradient, and phantom_hdri with camera_max_depth (the phantom test is
+ * depth == camera_max_depth, so it fires only for a ray traced at that depth;
+ * 0 = max_depth).  The environment and the lights are the uploaded scene's.
+ *
+ * The equality that defines it: take the float rays rt_extend_hits reports at
+ * bounce 0 for sample s of a camera (GetRay's rays), set id = y*W + x,
+ * samples = 1, sample_offset = s and copy the camera's background, sky,
+ * phantom and max_depth fields; then rgb is the frame rt_render writes for
+ * samples_per_pixel = 1, sample_offset = s, bit for bit, under every node
+ * format, schedule option, volume placement and RT_OPT_LIFT_PRIMS setting
+ * under which rt_render itself is invariant.
+ *
+ * Sums are fp64 per ray in sample order across batches, rounded to float once
+ * per call; accumulate != 0 adds double(rgb's previous value) to the sum
+ * before that rounding (rt_render_params.accumulate's rule).  The result does
+ * not depend on RT_OPT_BATCH_SLOTS, RT_OPT_STREAMS, RT_OPT_MAX_BLOCKS,
+ * RT_OPT_TAIL or RT_OPT_OVERLAP, nor on how the call cuts the ray array: n may
+ * exceed what one batch holds, and the call then renders consecutive ranges
+ * of the array in turn.  Neighbouring rays are traced together, so keep rays
+ * that are close in space close in the array (scanline or tile order).
+ *
+ * A ray with a non-finite origin or direction component, or a zero direction,
+ * traces nothing: it adds (0,0,0), raises no device error, and is counted in
+ * stats->invalid_rays (host variant only).
+ *
+ * The host variant blocks; it stages the arrays through buffers the context
+ * owns (grown on demand, freed with it).  The _device variant takes device
+ * arrays and is asynchronous on `hip_stream` (NULL = the context's stream); a
+ * device error surfaces as for rt_render_device.  rt_last_render_kernel_ms
+ * covers the call.  A multi-device context runs it on its first device.
+ * RT_ERR_INVALID: null pointers, n < 0 or n > 2^31 - 1, samples < 1,
+ * max_depth < 1, sample_offset < 0, camera_max_depth < 0, a non-finite
+ * background, or a ray's reserved != 0 (checked by the host variant only).
+ * n == 0 is RT_OK and launches nothing.  RT_ERR_NO_SCENE as for rt_render.
+ * Not offered (yet): per-ray tmin / tmax or time, moments or adaptive sampling
+ * over rays, feature buffers for rays, dealing rays over several devices, a
+ * keyed rt_trace_rays.                                                       */
+typedef struct rt_path_ray { float o[3]; uint32_t id; float d[3]; uint32_t reserved; } rt_path_ray;  /* 32 B */
+
+typedef struct rt_ray_color_params {
+  int32_t samples;          /* paths per ray, >= 1                                   */
+  int32_t max_depth;        /* the depth RayColor is called with, >= 1               */
+  int32_t sample_offset;    /* first sample index (RNG key), >= 0                    */
+  uint32_t seed;
+  int32_t accumulate;       /* as rt_render_params.accumulate                        */
+  int32_t use_sky_gradient; /* Camera.UseSkyGradient                                 */
+  int32_t phantom_hdri;     /* Camera.PhantomHDRI                                    */
+  int32_t camera_max_depth; /* Camera.MaxDepth for the PhantomHDRI test; 0 = max_depth */
+  double background[3];     /* Camera.Background                                     */
+} rt_ray_color_params;
+
+typedef struct rt_ray_color_stats { double kernel_ms; uint64_t samples; uint64_t invalid_rays; } rt_ray_color_stats;
+
+int rt_ray_color(rt_ctx* ctx, const rt_path_ray* rays, int64_t n, const rt_ray_color_params* params, float* rgb,
+                 rt_ray_color_stats* stats /* may be NULL */);
+int rt_ray_color_device(rt_ctx* ctx, const rt_path_ray* rays_dev, int64_t n, const rt_ray_color_params* params,
+                        float* rgb_dev, void* hip_stream);
+
 #ifdef __cplusplus
 }
 #endif
