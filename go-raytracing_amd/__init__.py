@@ -40,6 +40,7 @@ RT_OPT_DEALING, RT_OPT_DEAL_FIRST = 10, 11
 RT_OPT_TAIL = 12
 RT_OPT_OVERLAP = 13
 RT_OPT_LIFT_PRIMS = 14
+RT_OPT_EARLY_MISS = 15
 RT_PRIMS_LIFTED, RT_PRIMS_IN_BVH = 0, 1
 RT_DEAL_STATIC, RT_DEAL_DYNAMIC = 0, 1
 STATUS = {0: "RT_OK", -1: "RT_ERR_INVALID", -2: "RT_ERR_UNSUPPORTED", -3: "RT_ERR_HIP", -4: "RT_ERR_OOM",
@@ -231,7 +232,8 @@ class RtWorkCounts(C.Structure):
     _fields_ = [(n, C.c_uint64) for n in ("samples", "rays", "shadow_rays", "node_visits", "sphere_tests",
                                           "quad_tests", "tri_tests", "plane_tests", "instance_visits",
                                           "volume_tests", "material_fetches", "env_lookups",
-                                          "instance_box_tests", "stack_spills")]
+                                          "instance_box_tests", "stack_spills", "early_shadow_rays",
+                                          "early_rays")]
 
 
 class RtKernelTimes(C.Structure):
@@ -917,6 +919,14 @@ class Context:
         bounce b + 1's closest-hit kernel on a second stream per part.  Never
         changes the image."""
         self.set_option(RT_OPT_OVERLAP, mode)
+
+    def set_early_miss(self, mode: int = 0):
+        """RT_OPT_EARLY_MISS for the next renders: 0 automatic (on where it
+        applies), 1 off, 2 on.  The shade kernel resolves the rays that miss
+        the world BVH's box itself: an NEE job whose shadow rays all miss it is
+        applied in place, a path whose scattered ray misses it skips the
+        closest-hit kernel's queue.  Never changes the image."""
+        self.set_option(RT_OPT_EARLY_MISS, mode)
 
     def measure_read_bandwidth(self, nbytes: int = 4 << 30, reps: int = 10) -> float:
         """The measured HBM read peak (GB/s): `reps` coalesced passes over a

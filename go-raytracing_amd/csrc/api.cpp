@@ -519,6 +519,7 @@ int render_wave(rt_ctx* ctx, const DCamera& dc, const rt_render_params* p, const
     a.err = static_cast<int*>(ctx->errflag.p);
     a.refill = knobs.refill;
     a.nee_probe = run.probing ? 1u : 0u;
+    a.early_miss = early_miss_bits(knobs, early_miss_eligible(ctx->dscene), run.probing, lit, p->max_depth);
     a.spill_lanes = spill.lanes;
     a.spill_cap = spill.cap;
     a.out_pixels = run.rays ? run.rays->num_rays : uint32_t(dc.width) * uint32_t(dc.height);
@@ -956,6 +957,11 @@ int rt_ctx_set_option(rt_ctx* ctx, int32_t key, int32_t value) {
   if (key == RT_OPT_OVERLAP) {
     if (value < 0 || value > 2) return set_err(ctx, RT_ERR_INVALID, "overlap must be 0 (default), 1 (off) or 2 (on)");
     ctx->wopt.overlap = value;
+    return RT_OK;
+  }
+  if (key == RT_OPT_EARLY_MISS) {
+    if (value < 0 || value > 2) return set_err(ctx, RT_ERR_INVALID, "early miss must be 0 (default), 1 (off) or 2 (on)");
+    ctx->wopt.early_miss = value;
     return RT_OK;
   }
   if (key == RT_OPT_TAIL) {
@@ -1809,6 +1815,8 @@ void fill_counts(const unsigned long long* c, rt_work_counts* out) {
   out->env_lookups = c[11];
   out->instance_box_tests = c[12];
   out->stack_spills = c[13];
+  out->early_shadow_rays = c[14];
+  out->early_rays = c[15];
 }
 }  // namespace
 

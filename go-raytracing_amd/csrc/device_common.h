@@ -408,6 +408,8 @@ __device__ __forceinline__ bool tie_wins(const DScene& sc, int kind, int refpos,
 // Work counters for the instrumented variant (rt_count_work).
 struct Cnt {
   uint32_t rays, shadow, nodes, sph, quad, tri, plane, inst, vol, mat, env, ibox, spill;
+  uint32_t early_nee;   // k_shade: NEE rays it resolved itself (WaveArgs::early_miss)
+  uint32_t early_next;  // k_shade: next rays it kept out of k_extend's queue (the stream's back)
 };
 // Volume.Hit (volume.go:34-79) against a boundary given as an instance chain
 // over a list leaf.  ntests = how many times the enclosing leaf calls Hit
@@ -961,6 +963,23 @@ __device__ __forceinline__ Best trav_best(const Trav& T, const TStack& S) {
   return b;
 }
 
+// The root-box early-out of trav_init: true = the ray's interval [tmin, hi]
+// misses the world box, so its traversal ends at once with TRAV_DONE (a
+// closest-hit ray: hi = cull_widen(tmax); a shadow ray: hi = tmax).  The same
+// test in every node format.  On its own it decides the ray only in scenes
+// with the box test on and no plane (planes are tested before the box):
+// world_box_decides.  k_shade applies it to the rays it is about to queue
+// (WaveArgs::early_miss), from the very values the traversal kernels would
+// read back, so its answer is theirs.
+__device__ __forceinline__ bool world_box_missed(const DScene& sc, const TRay& r, float tmin, float hi) {
+  float tn = 0.0f;
+  return !box_hit(sc.tlas.box[0], sc.tlas.box[1], sc.tlas.box[2], sc.tlas.box[3], sc.tlas.box[4], sc.tlas.box[5], r, tmin,
+                  hi, tn);
+}
+__device__ __forceinline__ bool world_box_missed(const DScene& sc, V3 o, V3 d, float tmin, float hi) {
+  return world_box_missed(sc, make_tray(o, d), tmin, hi);
+}
+
 // Set up one ray: planes (lifted out of the BVH) and the root box.
 template <bool kAny, bool kCount, bool kWide = false>
 __device__ __forceinline__ int trav_init(const DScene& sc, Trav& T, const TStack& S, V3 wo, V3 wd, float time,
@@ -982,11 +1001,7 @@ __device__ __forceinline__ int trav_init(const DScene& sc, Trav& T, const TStack
   S.save_world(wo, wd, T.cr.inv);
   S.set_cur_ref(-1); T.sp = 0;
   T.item = ITEM_NONE; T.lf = ITEM_NONE;
-  float tn = 0.0f;
-  if (sc.tlas.check_box &&
-      !box_hit(sc.tlas.box[0], sc.tlas.box[1], sc.tlas.box[2], sc.tlas.box[3], sc.tlas.box[4], sc.tlas.box[5],
-               T.cr, tmin, kAny ? tmax : T.bt, tn))
-    return TRAV_DONE;
+  if (sc.tlas.check_box && world_box_missed(sc, T.cr, tmin, kAny ? tmax : T.bt)) return TRAV_DONE;
   T.item = kWide ? sc.root8 : sc.tlas.root_item;
   if ((T.item >> ITEM_SHIFT) != ITEM_NODE) {
     T.lf = T.item;

@@ -27,6 +27,7 @@ struct WaveOptions {
   int tail = 0;       // RT_OPT_TAIL: 0 automatic, 1 off, > 1 the rays-left threshold
   int streams = 0;    // RT_OPT_STREAMS: 1..kMaxTwins
   int overlap = 0;    // RT_OPT_OVERLAP: 0 automatic, 1 off, 2 on
+  int early_miss = 0; // RT_OPT_EARLY_MISS: 0 automatic, 1 off, 2 on
 };
 
 // The resolved knobs of one render: option, then environment, then automatic.
@@ -39,6 +40,7 @@ struct WaveKnobs {
   int debug_sync = 0;     // synchronise after every launch
   uint32_t tail_rays = 0; // k_tail takes over at most this many paths left (0 = never)
   int tail_first = kTailFirstDefault;
+  int early_miss = 0;     // rays that miss the world box resolved in k_shade: 1 off, anything else on where eligible
 };
 
 // The environment's tuning knobs, each the default of the option beside it:
@@ -54,9 +56,11 @@ struct WaveKnobs {
 //   RTGPU_TAIL_FIRST  -                  bounce of k_tail's extra rays-left check;
 //                                        unset kTailFirstDefault
 //   RTGPU_DEBUG_SYNC  -                  > 0: synchronise after every launch
+//   RTGPU_EARLY_MISS  RT_OPT_EARLY_MISS  1 off, 2 on
 struct WaveEnv {
   int streams, overlap, refill, max_blocks, tail_rays, tail_first, debug_sync;
   size_t slots;
+  int early_miss;
 };
 
 inline WaveEnv read_wave_env() {
@@ -74,6 +78,7 @@ inline WaveEnv read_wave_env() {
   v.tail_rays = tail >= 0 ? int(tail) : kTailRaysDefault;
   v.tail_first = int(num("RTGPU_TAIL_FIRST", kTailFirstDefault));
   v.debug_sync = num("RTGPU_DEBUG_SYNC", 0) > 0 ? 1 : 0;
+  v.early_miss = int(num("RTGPU_EARLY_MISS", 0));
   return v;
 }
 
@@ -95,6 +100,7 @@ inline WaveKnobs resolve_knobs(const WaveOptions& opt, bool probing, const WaveE
   k.debug_sync = env.debug_sync;
   k.tail_rays = probing || opt.tail == 1 ? 0u : uint32_t(opt.tail > 1 ? opt.tail : env.tail_rays);
   k.tail_first = env.tail_first;
+  k.early_miss = opt.early_miss ? opt.early_miss : env.early_miss;
   return k;
 }
 
@@ -124,6 +130,21 @@ inline uint64_t tile_pixels(const std::vector<int4>& tiles) {
 // "Bounce overlap": the full frame 2150 -> 2046 / 2025 Msamples/s on one / two
 // twins, 8-way shard sums 218.8 -> 223.7 / 230.7 ms).
 inline bool use_overlap(const WaveKnobs& k, bool lit) { return lit && k.overlap == 2; }
+
+// Rays that miss the world box resolved in k_shade (WaveArgs::early_miss;
+// DESIGN §3 "Rays that miss the world box"): the bits of the word.  On
+// unless turned off, in the renders where it is exact and pays: the scene is
+// eligible (`eligible`, early_miss_eligible: the root-box test alone decides
+// such a ray, and world primitives are lifted), and no path probe reads a
+// bounce's arrays (`probing`).
+// The survivors' part (EARLY_NEXT) stays off in a render that may hand its
+// paths to k_tail, which reads one range of the stream (run_batches: no
+// lights, a tail threshold, depth above 8).
+inline uint32_t early_miss_bits(const WaveKnobs& k, bool eligible, bool probing, bool lit, int max_depth) {
+  if (k.early_miss == 1 || !eligible || probing) return 0u;
+  const bool may_tail = !lit && k.tail_rays > 0 && max_depth > 8;
+  return EARLY_NEE | (may_tail ? 0u : EARLY_NEXT);
+}
 
 // Twins (wavefront.hip run_batches): tiles dealt in turn to `nt` parts of the
 // pixel list, each rendered on its own stream so one part's kernel tails

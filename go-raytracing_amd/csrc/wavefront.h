@@ -66,6 +66,17 @@ struct WaveArgs {
   int32_t spill_cap;
   uint32_t slots;   // capacity of every per-slot array (RTG_GUARD bounds checks)
   uint32_t out_pixels;  // pixels of the output frame (RTG_GUARD: k_finalize's scattered store)
+  // Rays that miss the world box (world_box_missed) resolved in k_shade
+  // instead of in the queues (RT_OPT_EARLY_MISS).  Bit 0
+  // (EARLY_NEE): an NEE job whose rays all miss it is applied by k_shade
+  // itself (k_shadow would answer "visible" at once) and not written.  Bit 1
+  // (EARLY_NEXT): a survivor whose next ray misses it goes to the back of the
+  // next stream, filled downwards from `slots` and counted in cnt_back; the
+  // next k_extend reads only the front, and the next k_shade shades a back
+  // entry with a miss for its hit record.  The host sets the bits only where
+  // the box test alone decides such a ray (world_box_decides) and no probe
+  // reads a bounce's arrays; 0 = every ray is queued.
+  uint32_t early_miss;
 };
 
 // Queue counters, each on its own 128-B line (same-line atomics serialise);
@@ -74,8 +85,13 @@ struct WaveArgs {
 // claim counters come in two sets, by bounce parity: bounce b's k_shadow /
 // k_nee_apply may still run while bounce b + 1's k_extend (which zeroes the
 // set of bounce b + 1) runs (WavePlan::overlap).
+// The back counts (WaveArgs::early_miss: survivors kept at the back of the
+// stream, which k_extend never sees) come in three sets, by bounce modulo 3:
+// k_shade b reads set b, adds to set b + 1 and zeroes set b + 2 for the next
+// bounce, so no other kernel has to reset them.
 enum : int { CNT_STREAM0 = 0, CNT_STREAM1 = 32, CNT_SHADOW = 64, CNT_FETCH_EXT = 128, CNT_FETCH_SH = 384,
-             CNT_SHADE_SEG = 896, CNT_WORDS_Q = 1152 };
+             CNT_SHADE_SEG = 896, CNT_BACK = 1152, CNT_WORDS_Q = 1248 };
+__host__ __device__ constexpr int cnt_back(uint32_t bounce) { return CNT_BACK + 32 * int(bounce % 3u); }
 __host__ __device__ constexpr int cnt_shadow(int parity) { return CNT_SHADOW + 32 * parity; }
 __host__ __device__ constexpr int cnt_fetch_sh(int parity) { return CNT_FETCH_SH + 256 * parity; }
 
@@ -112,7 +128,7 @@ struct WavePlan {
   const hipStream_t* aux;
   const hipEvent_t* ev_shade;
   const hipEvent_t* ev_nee;
-  uint32_t* probe_host;     // pinned words (one per twin) for the long-tail early exit
+  uint32_t* probe_host;     // pinned words (two per twin: [t] and [kMaxTwins + t]) for the long-tail early exit
   int* bounces_run;         // out (may be null): bounces the last batch ran (< max_depth after the early exit)
   // Per-launch timing (rt_set_kernel_timing): events 2k and 2k+1 are
   // recorded before and after one extend / shade / shadow launch on its
@@ -145,6 +161,7 @@ struct WavePlan {
   const RaySource* ray_src;
 };
 
+enum : uint32_t { EARLY_NEE = 1u, EARLY_NEXT = 2u };   // WaveArgs::early_miss
 enum : uint8_t { KC_EXTEND = 0, KC_SHADE = 1, KC_SHADOW = 2, KC_OTHER = 3 };
 constexpr int KC_TWIN_SHIFT = 4;   // ev_class bits 4-5: the twin that launched it
 // Most halves ("twins") a render's pixel list is split into, each on its own

@@ -90,9 +90,10 @@ __device__ __forceinline__ uint32_t lanes_below(unsigned long long m) {
 
 // counter block words: samples, then the Cnt fields in declaration order
 __device__ __forceinline__ void add_counters(unsigned long long* c, const Cnt& n, uint32_t samples) {
-  const uint32_t f[13] = {n.rays, n.shadow, n.nodes, n.sph, n.quad, n.tri, n.plane, n.inst, n.vol, n.mat, n.env, n.ibox, n.spill};
+  const uint32_t f[15] = {n.rays, n.shadow, n.nodes, n.sph, n.quad, n.tri, n.plane, n.inst, n.vol, n.mat, n.env, n.ibox, n.spill,
+                          n.early_nee, n.early_next};
   atomicAdd(c, (unsigned long long)samples);
-  for (int k = 0; k < 13; ++k) atomicAdd(c + 1 + k, (unsigned long long)f[k]);
+  for (int k = 0; k < 15; ++k) atomicAdd(c + 1 + k, (unsigned long long)f[k]);
 }
 
 // ---------------------------------------------------------------- camera
@@ -314,6 +315,31 @@ __device__ __forceinline__ void block_reserve2(bool c0, bool c1, uint32_t* q0, u
   __syncthreads();
   p0 = sb[0] + sw[0][w] + lanes_below(m0);
   p1 = sb[1] + sw[1][w] + lanes_below(m1);
+}
+
+// The same for three output queues (survivors at the front of the next
+// stream, survivors at its back, NEE jobs): the k_shade variants that read
+// WaveArgs::early_miss.  The back queue grows downwards from `slots`: a
+// block's run is contiguous, pb = slots - (base + total) + rank.
+__device__ __forceinline__ void block_reserve3(bool c0, bool cb, bool c1, uint32_t* q0, uint32_t* qb, uint32_t* q1,
+                                               uint32_t slots, uint32_t (*sw)[4], uint32_t* sb, uint32_t& p0, uint32_t& pb,
+                                               uint32_t& p1) {
+  const unsigned long long m0 = __ballot(c0), mb = __ballot(cb), m1 = __ballot(c1);
+  const int w = int(threadIdx.x >> 6);
+  if (__lane_id() == 0) { sw[0][w] = uint32_t(__popcll(m0)); sw[1][w] = uint32_t(__popcll(mb)); sw[2][w] = uint32_t(__popcll(m1)); }
+  __syncthreads();
+  // lanes 0 to 2 take one queue each: still one atomic instruction
+  for (uint32_t q = threadIdx.x; q < 3u; q += blockDim.x) {
+    const int nw = int((blockDim.x + 63u) >> 6);
+    uint32_t tot = 0;
+    for (int k = 0; k < nw; ++k) { const uint32_t c = sw[q][k]; sw[q][k] = tot; tot += c; }
+    const uint32_t base = tot ? atomicAdd(q == 0u ? q0 : q == 1u ? qb : q1, tot) : 0u;
+    sb[q] = q == 1u ? slots - (base + tot) : base;
+  }
+  __syncthreads();
+  p0 = sb[0] + sw[0][w] + lanes_below(m0);
+  pb = sb[1] + sw[1][w] + lanes_below(mb);
+  p1 = sb[2] + sw[2][w] + lanes_below(m1);
 }
 
 // k_shade claims its work in 256-path chunks, per block, from the segment of
@@ -609,9 +635,13 @@ static __global__ __launch_bounds__(256, SHADE_WAVES(kShadeL)) void k_shade(DSce
 #else
   extern __shared__ char s_dyn[];   // shade_lds_bytes(sc) per block (all records 16-B aligned, multiples of 16 B)
 #endif
-  __shared__ uint32_t s_w[2][2][4];
-  __shared__ uint32_t s_b[2][2];
   constexpr int kShade = kShadeL & SHADE_KIND_MASK;
+  // WaveArgs::early_miss is read only by the variants of scenes with lifted
+  // world primitives, the only ones the host sets it for (early_miss_eligible):
+  // every other variant is compiled without a trace of it
+  constexpr bool kEarly = (kShadeL & SHADE_LIFT) != 0;
+  __shared__ uint32_t s_w[2][kEarly ? 3 : 2][4];
+  __shared__ uint32_t s_b[2][kEarly ? 3 : 2];
   DScene sc = scg;
   // the lifted volumes' records (SHADE_VOL), read from global memory: their
   // addresses are uniform over the wave, so these are scalar loads (a copy in
@@ -626,11 +656,19 @@ static __global__ __launch_bounds__(256, SHADE_WAVES(kShadeL)) void k_shade(DSce
   if (kLdsTables || shade_tables_fit(sc)) shade_tables_to_lds(sc, s_dyn);
   const uint32_t n = *count;
   const uint32_t gs = gridDim.x * blockDim.x;
+  // WaveArgs::early_miss, EARLY_NEXT: this stream's back entries (bounce 0
+  // has no stream), the next stream's back count, and the set after it
+  // zeroed for the next bounce (k_shade b - 1 read it last; wavefront.h)
+  const bool back = kEarly && (a.early_miss & EARLY_NEXT) != 0u;
+  const uint32_t nb = (back && !kFirst) ? a.counts[cnt_back(launch_bounce)] : 0u;
+  uint32_t* const bcount = a.counts + cnt_back(launch_bounce + 1u);
   // reset the next extend's claim counters here: this bounce's k_extend has
   // finished claiming, and the next one starts after this kernel (k_shadow
   // may run beside the next k_extend, WavePlan::overlap)
-  if (blockIdx.x == 0 && threadIdx.x == 0)
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
     for (uint32_t k = 0; k < kSegs; ++k) a.counts[CNT_FETCH_EXT + k * kSegStride] = 0u;
+    if (back) a.counts[cnt_back(launch_bounce + 2u)] = 0u;
+  }
   Cnt cnt = {};
   // block-uniform trip count (blockDim 256, gs a multiple of 256): every
   // thread reaches the block_reserve2 barriers
@@ -639,14 +677,17 @@ static __global__ __launch_bounds__(256, SHADE_WAVES(kShadeL)) void k_shade(DSce
   (void)gs;
   __shared__ uint32_t s_chunk[2];   // double-buffered like s_w / s_b
   uint32_t seg = xcc_id(), tried = 0;
-  const uint32_t nchunks = n_up / blockDim.x;
+  // the front's chunks, then the back's
+  const uint32_t fchunks = n_up / blockDim.x;
+  const uint32_t nchunks = fchunks + ((nb + 255u) & ~255u) / blockDim.x;
   if (threadIdx.x == 0) s_chunk[0] = shade_claim(a.counts + CNT_SHADE_SEG, nchunks, seg, tried);
   for (;; par ^= 1u) {
     __syncthreads();
     const uint32_t chunk = s_chunk[par];
     if (chunk == 0xFFFFFFFFu) break;   // block-uniform
-    const uint32_t i = chunk * blockDim.x + threadIdx.x;
-    const bool live = i < n;
+    const bool bchunk = kEarly && chunk >= fchunks;   // block-uniform
+    const uint32_t i = (bchunk ? chunk - fchunks : chunk) * blockDim.x + threadIdx.x;
+    const bool live = i < (bchunk ? nb : n);
     bool cont = false, want_shadow = false;
     uint32_t slot = 0, key = 0, flags = 0, bounce = 0, nstate = 0;
     float tmax_a = 0.0f;
@@ -654,8 +695,10 @@ static __global__ __launch_bounds__(256, SHADE_WAVES(kShadeL)) void k_shade(DSce
     bool lout_set = false;
     if (live) {
       if (kCount) cnt.rays++;                                    // paths shaded
-      const uint32_t ii = GIX(i, a.slots, 41);
-      const float4 h = ldnt(&a.hit[ii]);
+      // a back entry was never traced: its ray misses the world box, and its
+      // hit record is the miss k_extend would have stored for it (store_hit)
+      const uint32_t ii = GIX(bchunk ? a.slots - nb + i : i, a.slots, 41);
+      const float4 h = bchunk ? make_float4(__builtin_inff(), 0.0f, asf(0xFFFFFFFFu), 0.0f) : ldnt(&a.hit[ii]);
       // the block's next chunk, claimed beside the hit load and published by
       // the next iteration's barrier: the claim's round trip no longer holds
       // every wave of the block there
@@ -696,9 +739,49 @@ static __global__ __launch_bounds__(256, SHADE_WAVES(kShadeL)) void k_shade(DSce
     // (thread 0 is live in every chunk of a 256-thread block; the host
     // emulation's one-thread blocks also reach the chunks past n)
     if (!live && threadIdx.x == 0) s_chunk[par ^ 1u] = shade_claim(a.counts + CNT_SHADE_SEG, nchunks, seg, tried);
+    // WaveArgs::early_miss: a job whose rays all miss the world box needs no
+    // k_shadow (trav_init would end each of them there, "visible") and no
+    // k_nee_apply: this thread, the only writer of Lout[slot] in this kernel,
+    // makes k_nee_apply's add itself and writes no job.  A job with a ray that
+    // passes the box is queued whole, as ever.  The radiance is loaded here so
+    // that its latency hides under the reservation's round trip; a path that
+    // samples a light has added nothing to it in shade_path, and at bounce 0
+    // the sum is stored in place of the zero.
+    bool early = false;
+    float4 l4 = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    if (kEarly && (a.early_miss & EARLY_NEE) && want_shadow) {
+      early = !(flags & 1u) || world_box_missed(sc, P, da, 0.001f, tmax_a);
+      if (kEnvIS && (flags & 2u)) early = early && world_box_missed(sc, P, dh, 0.001f, __builtin_inff());
+      if (early) {
+        want_shadow = false;
+        lout_set = true;
+        if (!kFirst) l4 = ldnt(&a.Lout[GIX(slot, a.slots, 44)]);
+        if (kCount) cnt.early_nee += (flags & 1u) + ((flags >> 1) & 1u);   // NEE rays resolved here
+      }
+    }
     if (kFirst && live && !lout_set) stnt(&a.Lout[GIX(slot, a.slots, 44)], make_float4(0.0f, 0.0f, 0.0f, 0.0f));
-    uint32_t jc = 0, js = 0;
-    block_reserve2(cont, want_shadow, ncount, jcount, s_w[par], s_b[par], jc, js);
+    // EARLY_NEXT: a survivor whose next ray misses the world box (k_extend's
+    // trav_init would end it there, a miss) goes to the back of the stream
+    const bool cback = back && cont && world_box_missed(sc, P, sd, 0.001f, cull_widen(__builtin_inff()));
+    if (kCount && cback) cnt.early_next++;
+    uint32_t jc = 0, jb = 0, js = 0;
+    if constexpr (kEarly) {
+      block_reserve3(cont && !cback, cback, want_shadow, ncount, bcount, jcount, a.slots, s_w[par], s_b[par], jc, jb, js);
+      if (cback) jc = jb;
+    } else {
+      block_reserve2(cont, want_shadow, ncount, jcount, s_w[par], s_b[par], jc, js);
+    }
+    if (early) {   // k_nee_apply's sum, in its order
+      V3 direct = mul(beta, ca);
+      if (kEnvIS) {
+        direct = mk(0.0f, 0.0f, 0.0f);
+        if (flags & 2u) direct = add(direct, ch);
+        if (flags & 1u) direct = add(direct, ca);
+        direct = mul(beta, direct);
+      }
+      const V3 L = add(mk(l4.x, l4.y, l4.z), direct);
+      stnt(&a.Lout[GIX(slot, a.slots, 44)], make_float4(L.x, L.y, L.z, 0.0f));
+    }
     if (cont) {
       jc = GIX(jc, a.slots, 43);
       stnt(&ns.o[jc], make_float4(P.x, P.y, P.z, asf(slot)));
@@ -978,6 +1061,7 @@ static __global__ __launch_bounds__(256) void k_finalize(WaveArgs a, float* out,
 static __global__ void k_set_counts(uint32_t* c, uint32_t n) {
   if (threadIdx.x == 0) {
     c[CNT_STREAM0] = n; c[CNT_STREAM1] = 0u; c[cnt_shadow(0)] = 0u; c[cnt_shadow(1)] = 0u;
+    for (uint32_t k = 0; k < 3u; ++k) c[cnt_back(k)] = 0u;
     for (uint32_t k = 0; k < kSegs; ++k) {
       c[CNT_FETCH_EXT + k * kSegStride] = 0u;
       c[cnt_fetch_sh(0) + k * kSegStride] = 0u;
@@ -1188,14 +1272,23 @@ static hipError_t run_batches(const WaveKernels& k, const DScene& sc, const DCam
       if (plan.max_depth > 8 && ((b >= 7 && (b % 4) == 3) || (plan.tail_rays > 0 && b == plan.tail_first))) {
         // long-tail scenes (RandomScene depth 50): stop once every path of
         // every twin ended
-        for (int t = 0; t < nt; ++t)
+        // (the paths left are the next stream's front and, with WaveArgs::
+        // early_miss, its back: probe_host[kMaxTwins + t])
+        for (int t = 0; t < nt; ++t) {
           if ((e = hipMemcpyAsync(plan.probe_host + t, as[t].counts + (nx ? CNT_STREAM1 : CNT_STREAM0), sizeof(uint32_t),
                                   hipMemcpyDeviceToHost, sts[t])) != hipSuccess)
             return e;
+          plan.probe_host[kMaxTwins + t] = 0u;
+          if ((as[t].early_miss & EARLY_NEXT) &&
+              (e = hipMemcpyAsync(plan.probe_host + kMaxTwins + t, as[t].counts + cnt_back(uint32_t(b) + 1u), sizeof(uint32_t),
+                                  hipMemcpyDeviceToHost, sts[t])) != hipSuccess)
+            return e;
+        }
         uint32_t left = 0;
         uint32_t lefts[kMaxTwins] = {};
         for (int t = 0; t < nt; ++t) {
           if ((e = hipStreamSynchronize(sts[t])) != hipSuccess) return e;
+          plan.probe_host[t] += plan.probe_host[kMaxTwins + t];
           left += plan.probe_host[t];
           lefts[t] = plan.probe_host[t];
           // the counts only shrink from here: size the persistent grids for

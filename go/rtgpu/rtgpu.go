@@ -110,6 +110,7 @@ const (
 	OptTail         int32 = 12 // RT_OPT_TAIL
 	OptOverlap      int32 = 13 // RT_OPT_OVERLAP
 	OptLiftPrims    int32 = 14 // RT_OPT_LIFT_PRIMS
+	OptEarlyMiss    int32 = 15 // RT_OPT_EARLY_MISS
 	PrimsLifted     int32 = 0  // RT_PRIMS_LIFTED
 	PrimsInBVH      int32 = 1  // RT_PRIMS_IN_BVH
 	DealStatic      int32 = 0  // RT_DEAL_STATIC

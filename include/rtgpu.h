@@ -224,6 +224,9 @@ typedef struct rt_work_counts {
   uint64_t material_fetches, env_lookups;
   uint64_t instance_box_tests; /* world-space instance culling boxes (32 B)  */
   uint64_t stack_spills;       /* traversal-stack pushes past the LDS ring (to the global spill area) */
+  uint64_t early_shadow_rays;  /* NEE rays the shade kernel resolved itself (RT_OPT_EARLY_MISS): they
+                                  missed the world box and never reached the shadow kernel */
+  uint64_t early_rays;         /* scattered rays it kept out of the closest-hit kernel's queue likewise */
 } rt_work_counts;
 
 /* Summed per-launch durations of the wavefront kernels of the last render
@@ -406,11 +409,25 @@ int rt_last_dealing(const rt_ctx* ctx, int32_t* tiles, int32_t* runs, int32_t ma
  *     camera.go:443-518).  Same operations per path in the same order: the
  *     frame is bit-identical.  0 (default) = automatic (off: measured
  *     slower on CornellBoxLucy), 1 = off, 2 = on (at most two
- *     parts unless RT_OPT_STREAMS says otherwise).                       */
+ *     parts unless RT_OPT_STREAMS says otherwise).
+ *   RT_OPT_EARLY_MISS: rays that miss the box of the world BVH are
+ *     resolved by the shade kernel that makes them, since the traversal
+ *     would end each at its first test.  An NEE job whose shadow rays all
+ *     miss it ("visible") is applied there instead of being queued for
+ *     k_shadow and k_nee_apply; a path whose scattered ray misses it is kept
+ *     at the back of the next stream, which k_extend does not read, and is
+ *     shaded at the next bounce as the miss it is.  The test is the
+ *     traversal's own, on the values it would read back, and the adds are
+ *     the same in the same order: the frame is bit-identical.  Only in
+ *     scenes without planes (they are tested before the box) and never in
+ *     the path probes' renders; the scattered rays' part is off in renders
+ *     that may use the long-tail kernel (RT_OPT_TAIL).
+ *     0 (default) = automatic (on where it applies), 1 = off, 2 = on.      */
 enum { RT_OPT_BLAS_BUILDER = 1, RT_OPT_TLAS_BUILDER = 2, RT_OPT_NODE_FORMAT = 3,
        RT_OPT_BATCH_SLOTS = 4, RT_OPT_REFILL = 5, RT_OPT_MAX_BLOCKS = 6, RT_OPT_STREAMS = 7,
        RT_OPT_VOLUMES = 8, RT_OPT_BVH4_COLLAPSE = 9, RT_OPT_DEALING = 10, RT_OPT_DEAL_FIRST = 11,
-       RT_OPT_TAIL = 12, RT_OPT_OVERLAP = 13, RT_OPT_LIFT_PRIMS = 14 };
+       RT_OPT_TAIL = 12, RT_OPT_OVERLAP = 13, RT_OPT_LIFT_PRIMS = 14,
+       RT_OPT_EARLY_MISS = 15 };
 enum { RT_PRIMS_LIFTED = 0, RT_PRIMS_IN_BVH = 1 };
 enum { RT_DEAL_STATIC = 0, RT_DEAL_DYNAMIC = 1 };
 enum { RT_BLAS_REFERENCE = 0, RT_BLAS_SAH = 1, RT_BLAS_DEVICE = 2 };
@@ -462,8 +479,10 @@ int rt_count_work(rt_ctx* ctx, const rt_camera_desc* cam, const rt_render_params
 
 /* Same instrumented run, counters split by kernel: out[0] = extend
  * (closest-hit traversal, camera rays), out[1] = shade (materials, NEE
- * set-up, HDRI lookups; there `rays` counts the paths shaded and
- * `shadow_rays` the NEE jobs written), out[2] = shadow (any-hit traversal).
+ * set-up, HDRI lookups; there `rays` counts the paths shaded,
+ * `shadow_rays` the NEE jobs written, `early_shadow_rays` the NEE rays it
+ * resolved without a job and `early_rays` the next rays it kept out of the
+ * extend kernel's queue, RT_OPT_EARLY_MISS), out[2] = shadow (any-hit traversal).
  * rt_count_work's `rays` / `shadow_rays` are the extend and shadow ones.   */
 int rt_count_work_by_kernel(rt_ctx* ctx, const rt_camera_desc* cam, const rt_render_params* params,
                             rt_work_counts out[3]);
