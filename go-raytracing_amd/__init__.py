@@ -228,6 +228,46 @@ def ray_color_params(samples: int, depth: int, seed: int = 1, sample_offset: int
     return p
 
 
+# rt_gather's direction sources
+RT_GATHER_RAY = 0
+RT_GATHER_COSINE = 1
+RT_GATHER_SPHERE = 2
+
+
+class RtGatherPoint(C.Structure):
+    """rt_gather_point (32 B, rt_path_ray's layout): position, id (the RNG key's pixel word), normal, reserved (0)."""
+    _fields_ = [("p", C.c_float * 3), ("id", C.c_uint32), ("n", C.c_float * 3), ("reserved", C.c_uint32)]
+
+
+class RtGatherParams(C.Structure):
+    _fields_ = [("path", RtRayColorParams), ("source", C.c_int32), ("reserved", C.c_int32)]
+
+
+GATHER_POINT_DTYPE = np.dtype([("p", np.float32, 3), ("id", np.uint32), ("n", np.float32, 3), ("reserved", np.uint32)])
+
+
+def make_gather_points(p, n, ids=None) -> np.ndarray:
+    """An array of rt_gather_point (GATHER_POINT_DTYPE) from positions and
+    normals (n, 3); ids: each point's RNG key word (default: its index)."""
+    p = np.asarray(p, np.float32).reshape(-1, 3)
+    n = np.asarray(n, np.float32).reshape(-1, 3)
+    if p.shape != n.shape:
+        raise ValueError("positions and normals differ in shape")
+    pts = np.zeros(p.shape[0], GATHER_POINT_DTYPE)
+    pts["p"], pts["n"] = p, n
+    pts["id"] = np.arange(p.shape[0], dtype=np.uint32) if ids is None else np.asarray(ids, np.uint32).reshape(-1)
+    return pts
+
+
+def gather_params(source: int, samples: int, depth: int, seed: int = 1, sample_offset: int = 0, camera=None,
+                  accumulate: bool = False, **sky) -> RtGatherParams:
+    """rt_gather_params: `source` (RT_GATHER_*) and the path fields of ray_color_params."""
+    g = RtGatherParams()
+    g.path = ray_color_params(samples, depth, seed, sample_offset, camera, accumulate, **sky)
+    g.source = source
+    return g
+
+
 class RtWorkCounts(C.Structure):
     _fields_ = [(n, C.c_uint64) for n in ("samples", "rays", "shadow_rays", "node_visits", "sphere_tests",
                                           "quad_tests", "tri_tests", "plane_tests", "instance_visits",
@@ -361,6 +401,11 @@ def rtgpu() -> C.CDLL:
             lib.rt_ray_color.argtypes = [P, C.POINTER(RtPathRay), C.c_int64, C.POINTER(RtRayColorParams),
                                          C.POINTER(C.c_float), C.POINTER(RtRayColorStats)]
             lib.rt_ray_color_device.argtypes = [P, P, C.c_int64, C.POINTER(RtRayColorParams), P, P]
+        if hasattr(lib, "rt_gather"):
+            lib.rt_gather.argtypes = [P, C.POINTER(RtGatherPoint), C.c_int64, C.POINTER(RtGatherParams),
+                                      C.POINTER(C.c_float), C.POINTER(RtRayColorStats)]
+            lib.rt_gather_device.argtypes = [P, P, C.c_int64, C.POINTER(RtGatherParams), P, P]
+            lib.rt_gather_rays.argtypes = [P, C.POINTER(RtGatherPoint), C.c_int64, I32, U32, I32, C.POINTER(RtPathRay)]
         _rtgpu = lib
     return _rtgpu
 
@@ -1054,6 +1099,41 @@ class Context:
         floats at rgb_ptr, asynchronous on `stream`."""
         self._check(self._lib.rt_ray_color_device(self._h, C.c_void_p(rays_ptr), n, C.byref(params),
                                                   C.c_void_p(rgb_ptr), C.c_void_p(stream)))
+
+    # ---- path integrals over directions drawn on the device (rt_gather)
+    def gather(self, pts: np.ndarray, source: int, samples: int, depth: int, seed: int = 1, sample_offset: int = 0,
+               camera=None, accum: Optional[np.ndarray] = None, **sky):
+        """rt_gather: pts is an array of rt_gather_point (GATHER_POINT_DTYPE,
+        make_gather_points); returns the (n, 3) float32 sums over `samples`
+        paths per point, each along a direction `source` draws for it, and the
+        stats.  COSINE: irradiance = pi * rgb / samples; SPHERE: the mean over
+        the sphere = rgb / samples.  The rest as ray_color."""
+        pts = np.ascontiguousarray(pts, GATHER_POINT_DTYPE)
+        n = pts.shape[0]
+        p = gather_params(source, samples, depth, seed, sample_offset, camera, accum is not None, **sky)
+        if accum is None:
+            accum = np.zeros((n, 3), np.float32)
+        if accum.dtype != np.float32 or accum.size != 3 * n or not accum.flags["C_CONTIGUOUS"]:
+            raise ValueError("accum must be a contiguous float32 array of 3 floats per point")
+        st = RtRayColorStats()
+        self._check(self._lib.rt_gather(self._h, pts.ctypes.data_as(C.POINTER(RtGatherPoint)), n, C.byref(p),
+                                        _f32p(accum), C.byref(st)))
+        return accum, st
+
+    def gather_device(self, pts_ptr: int, n: int, params: RtGatherParams, rgb_ptr: int, stream: int = 0):
+        """rt_gather_device: n rt_gather_point at device address pts_ptr -> 3 n
+        floats at rgb_ptr, asynchronous on `stream`."""
+        self._check(self._lib.rt_gather_device(self._h, C.c_void_p(pts_ptr), n, C.byref(params), C.c_void_p(rgb_ptr),
+                                               C.c_void_p(stream)))
+
+    def gather_rays(self, pts: np.ndarray, source: int, seed: int = 1, sample: int = 0) -> np.ndarray:
+        """rt_gather_rays: the rt_path_ray (PATH_RAY_DTYPE) that sample `sample`
+        of every point traces; needs no uploaded scene."""
+        pts = np.ascontiguousarray(pts, GATHER_POINT_DTYPE)
+        out = np.zeros(pts.shape[0], PATH_RAY_DTYPE)
+        self._check(self._lib.rt_gather_rays(self._h, pts.ctypes.data_as(C.POINTER(RtGatherPoint)), pts.shape[0], source,
+                                             seed, sample, out.ctypes.data_as(C.POINTER(RtPathRay))))
+        return out
 
 
 # ---------------------------------------------------------------------------

@@ -136,7 +136,8 @@ struct rt_ctx {
   hipEvent_t q_ev = nullptr;
   hipStream_t q_st = nullptr;
   bool q_pending = false;
-  // rt_ray_color's host variant: its staging copies of the rays and the sums;
+  // rt_ray_color's and rt_gather's host variants: their staging copies of the
+  // records and the sums (rt_gather_rays: of the points and the rays);
   // rc_ev follows the latest call's work on rc_st, so a call on another stream
   // starts after it (they share the batch buffers)
   DevBuf rc_rays, rc_rgb;
@@ -2217,9 +2218,10 @@ int ray_color_check(rt_ctx* ctx, const rt_ray_color_params* p, int64_t n, DCamer
 // sample of every ray of a range, so the array is cut into consecutive ranges
 // of at most the batch's slots; each range is one render over the identity
 // list (ray k of the range -> rgb[3k]), with all its samples, so a ray's sum
-// never depends on the cut.
-int ray_color_device(rt_ctx* ctx, const DCamera& dc, const rt_path_ray* rays, int64_t n, const rt_ray_color_params* p,
-                     float* rgb, hipStream_t st) {
+// never depends on the cut.  kind (ray_source.h's SRC_*): the records are rays
+// (rt_ray_color) or rt_gather's points under one of its sources.
+int ray_color_device(rt_ctx* ctx, const DCamera& dc, int32_t kind, const rt_path_ray* rays, int64_t n,
+                     const rt_ray_color_params* p, float* rgb, hipStream_t st) {
   const bool lit = ctx->dscene.num_lights > 0;
   const WaveKnobs knobs = resolve_knobs(ctx->wopt, false);
   size_t target = knobs.slots;
@@ -2247,6 +2249,7 @@ int ray_color_device(rt_ctx* ctx, const DCamera& dc, const rt_path_ray* rays, in
     RaySource src{};
     src.rays = reinterpret_cast<const float4*>(rays + off);
     src.num_rays = uint32_t(std::min<int64_t>(range, n - off));
+    src.kind = kind;
     RenderRun run{st};
     run.from_list = true;
     run.list_n = src.num_rays;
@@ -2257,6 +2260,56 @@ int ray_color_device(rt_ctx* ctx, const DCamera& dc, const rt_path_ray* rays, in
   ctx->rc_st = st;
   ctx->rc_pending = true;
   return RT_OK;
+}
+
+// The host variants behind their checks: n host records (rays, or rt_gather's
+// points: the same 32 B) staged through the context's buffers, traced, copied
+// back; blocks.  invalid: the records the kernel's guard will leave out.
+int ray_color_host(rt_ctx* ctx, const DCamera& dc, int32_t kind, const void* recs, int64_t n, const rt_ray_color_params* params,
+                   float* rgb, rt_ray_color_stats* stats, uint64_t invalid) {
+  int rc = check_render_error(ctx, true);
+  if (rc) return rc;
+  double ms = 0.0;
+  if (n > 0) {
+    hipStream_t st = ctx->stream;
+    if ((rc = ensure(ctx, ctx->rc_rays, size_t(n) * sizeof(rt_path_ray)))) return rc;
+    if ((rc = ensure(ctx, ctx->rc_rgb, size_t(n) * 3 * sizeof(float)))) return rc;
+    HIPCHK(hipMemcpyAsync(ctx->rc_rays.p, recs, size_t(n) * sizeof(rt_path_ray), hipMemcpyHostToDevice, st));
+    if (params->accumulate)
+      HIPCHK(hipMemcpyAsync(ctx->rc_rgb.p, rgb, size_t(n) * 3 * sizeof(float), hipMemcpyHostToDevice, st));
+    if ((rc = ray_color_device(ctx, dc, kind, static_cast<const rt_path_ray*>(ctx->rc_rays.p), n, params,
+                               static_cast<float*>(ctx->rc_rgb.p), st)))
+      return rc;
+    HIPCHK(hipMemcpyAsync(rgb, ctx->rc_rgb.p, size_t(n) * 3 * sizeof(float), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    if ((rc = check_render_error(ctx, true))) return rc;
+    float f = 0.f;
+    HIPCHK(hipEventElapsedTime(&f, ctx->kev0, ctx->kev1));
+    ms = f;
+  }
+  if (stats) {
+    stats->kernel_ms = ms;
+    stats->samples = uint64_t(n) * uint64_t(params->samples);
+    stats->invalid_rays = invalid;
+  }
+  return RT_OK;
+}
+
+// rt_gather's own refusals (the rest are ray_color_check's).
+int gather_check(rt_ctx* ctx, int32_t source, int32_t reserved) {
+  if (source < RT_GATHER_RAY || source > RT_GATHER_SPHERE) return set_err(ctx, RT_ERR_INVALID, "gather source outside 0 .. 2");
+  if (reserved != 0) return set_err(ctx, RT_ERR_INVALID, "rt_gather_params.reserved is not 0");
+  return RT_OK;
+}
+
+// source_ray's guard (ray_source.hip) for the host variant's count; fp32 in its order.
+bool gather_point_valid(const rt_gather_point& q, int32_t source) {
+  if (!(std::isfinite(q.p[0]) && std::isfinite(q.p[1]) && std::isfinite(q.p[2]))) return false;
+  if (source == RT_GATHER_SPHERE) return true;
+  if (!(std::isfinite(q.n[0]) && std::isfinite(q.n[1]) && std::isfinite(q.n[2]))) return false;
+  const float xx = q.n[0] * q.n[0], yy = q.n[1] * q.n[1], zz = q.n[2] * q.n[2];
+  const float l = sqrtf((xx + yy) + zz);
+  return l != 0.0f && std::isfinite(l);
 }
 
 }  // namespace
@@ -2302,31 +2355,7 @@ int rt_ray_color(rt_ctx* ctx, const rt_path_ray* rays, int64_t n, const rt_ray_c
                      std::isfinite(r.d[1]) && std::isfinite(r.d[2]);
     invalid += !(fin && (r.d[0] != 0.0f || r.d[1] != 0.0f || r.d[2] != 0.0f));   // k_ray_source's guard
   }
-  if ((rc = check_render_error(ctx, true))) return rc;
-  double ms = 0.0;
-  if (n > 0) {
-    hipStream_t st = ctx->stream;
-    if ((rc = ensure(ctx, ctx->rc_rays, size_t(n) * sizeof(rt_path_ray)))) return rc;
-    if ((rc = ensure(ctx, ctx->rc_rgb, size_t(n) * 3 * sizeof(float)))) return rc;
-    HIPCHK(hipMemcpyAsync(ctx->rc_rays.p, rays, size_t(n) * sizeof(rt_path_ray), hipMemcpyHostToDevice, st));
-    if (params->accumulate)
-      HIPCHK(hipMemcpyAsync(ctx->rc_rgb.p, rgb, size_t(n) * 3 * sizeof(float), hipMemcpyHostToDevice, st));
-    if ((rc = ray_color_device(ctx, dc, static_cast<const rt_path_ray*>(ctx->rc_rays.p), n, params,
-                               static_cast<float*>(ctx->rc_rgb.p), st)))
-      return rc;
-    HIPCHK(hipMemcpyAsync(rgb, ctx->rc_rgb.p, size_t(n) * 3 * sizeof(float), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    if ((rc = check_render_error(ctx, true))) return rc;
-    float f = 0.f;
-    HIPCHK(hipEventElapsedTime(&f, ctx->kev0, ctx->kev1));
-    ms = f;
-  }
-  if (stats) {
-    stats->kernel_ms = ms;
-    stats->samples = uint64_t(n) * uint64_t(params->samples);
-    stats->invalid_rays = invalid;
-  }
-  return RT_OK;
+  return ray_color_host(ctx, dc, SRC_CALLER, rays, n, params, rgb, stats, invalid);
 }
 
 int rt_ray_color_device(rt_ctx* ctx, const rt_path_ray* rays_dev, int64_t n, const rt_ray_color_params* params,
@@ -2338,7 +2367,63 @@ int rt_ray_color_device(rt_ctx* ctx, const rt_path_ray* rays_dev, int64_t n, con
   int rc = ray_color_check(ctx, params, n, dc);
   // an earlier call's device error surfaces here at the latest, as in rt_render_device
   if (rc || (rc = check_render_error(ctx, false)) || n == 0) return rc;
-  return ray_color_device(ctx, dc, rays_dev, n, params, rgb_dev, st);
+  return ray_color_device(ctx, dc, SRC_CALLER, rays_dev, n, params, rgb_dev, st);
+}
+
+// ---- rt_gather: rt_ray_color over directions ray_source.hip draws ----------
+
+static_assert(sizeof(rt_gather_point) == sizeof(rt_path_ray) && sizeof(rt_gather_params) == 64, "rt_gather_point is rt_path_ray's layout");
+static_assert(SRC_RAY == 1 + RT_GATHER_RAY && SRC_COSINE == 1 + RT_GATHER_COSINE && SRC_SPHERE == 1 + RT_GATHER_SPHERE,
+              "ray_source.h's kinds follow rtgpu.h's sources");
+
+int rt_gather(rt_ctx* ctx, const rt_gather_point* pts, int64_t n, const rt_gather_params* params, float* rgb,
+              rt_ray_color_stats* stats) {
+  if (!ctx || !pts || !params || !rgb) return RT_ERR_INVALID;
+  HIPCHK(hipSetDevice(ctx->device));
+  if (int rc = gather_check(ctx, params->source, params->reserved)) return rc;
+  DCamera dc{};
+  int rc = ray_color_check(ctx, &params->path, n, dc);
+  if (rc) return rc;
+  uint64_t invalid = 0;
+  for (int64_t i = 0; i < n; ++i) {
+    if (pts[i].reserved != 0) return set_err(ctx, RT_ERR_INVALID, "a point's reserved word is not 0");
+    invalid += !gather_point_valid(pts[i], params->source);
+  }
+  return ray_color_host(ctx, dc, 1 + params->source, pts, n, &params->path, rgb, stats, invalid);
+}
+
+int rt_gather_device(rt_ctx* ctx, const rt_gather_point* pts_dev, int64_t n, const rt_gather_params* params,
+                     float* rgb_dev, void* hip_stream) {
+  if (!ctx || !pts_dev || !params || !rgb_dev) return RT_ERR_INVALID;
+  HIPCHK(hipSetDevice(ctx->device));
+  hipStream_t st = hip_stream ? static_cast<hipStream_t>(hip_stream) : ctx->stream;
+  if (int rc = gather_check(ctx, params->source, params->reserved)) return rc;
+  DCamera dc{};
+  int rc = ray_color_check(ctx, &params->path, n, dc);
+  if (rc || (rc = check_render_error(ctx, false)) || n == 0) return rc;
+  return ray_color_device(ctx, dc, 1 + params->source, reinterpret_cast<const rt_path_ray*>(pts_dev), n, &params->path,
+                          rgb_dev, st);
+}
+
+int rt_gather_rays(rt_ctx* ctx, const rt_gather_point* pts, int64_t n, int32_t source, uint32_t seed, int32_t sample,
+                   rt_path_ray* out) {
+  if (!ctx || !pts || !out) return RT_ERR_INVALID;
+  HIPCHK(hipSetDevice(ctx->device));
+  if (int rc = gather_check(ctx, source, 0)) return rc;
+  if (n < 0 || n > kRayColorMaxRays) return set_err(ctx, RT_ERR_INVALID, "point count outside 0 .. 2^31 - 1");
+  if (sample < 0) return set_err(ctx, RT_ERR_INVALID, "bad sample index");
+  if (n == 0) return RT_OK;
+  // the staging buffers of the host variants: the points in rc_rays, the rays in rc_rgb
+  hipStream_t st = ctx->stream;
+  const size_t bytes = size_t(n) * sizeof(rt_path_ray);
+  int rc = ensure(ctx, ctx->rc_rays, bytes);
+  if (rc || (rc = ensure(ctx, ctx->rc_rgb, bytes))) return rc;
+  HIPCHK(hipMemcpyAsync(ctx->rc_rays.p, pts, bytes, hipMemcpyHostToDevice, st));
+  HIPCHK(launch_gather_rays(static_cast<const float4*>(ctx->rc_rays.p), uint32_t(n), 1 + source, seed, uint32_t(sample),
+                            static_cast<float4*>(ctx->rc_rgb.p), ctx->num_cus, st));
+  HIPCHK(hipMemcpyAsync(out, ctx->rc_rgb.p, bytes, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  return RT_OK;
 }
 
 }  // extern "C"

@@ -517,6 +517,7 @@ enum : uint32_t {
   DOM_VOL = 4,      // vol_id*4 + pass (closest-hit ray)
   DOM_VOL_SH_AREA = 5,
   DOM_VOL_SH_HDRI = 6,
+  DOM_SOURCE = 7,   // bounce 0 only; 3k..3k+2: RandomUnitVector try k of rt_gather's direction
 };
 constexpr int MAX_UNIT_TRIES = 64;
 constexpr int MAX_DISK_TRIES = 64;

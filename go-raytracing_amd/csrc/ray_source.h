@@ -1,5 +1,6 @@
-// ray_source.h — launch interface of ray_source.hip: the caller's rays as
-// bounce 0 of the wavefront pipeline (rt_ray_color).
+// ray_source.h — launch interface of ray_source.hip: the caller's rays, or rays
+// drawn on the device from the caller's points, as bounce 0 of the wavefront
+// pipeline (rt_ray_color, rt_gather).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -7,18 +8,27 @@
 
 namespace rtg {
 
-// The rays of one rt_ray_color range.  A ray is two float4 (rt_path_ray:
-// origin.xyz, id; direction.xyz, reserved), indexed by the entries of the
-// twin's "pixel list" (WaveArgs::pixels), which name rays of this range.  Its
-// own struct, like QueryArgs: WaveArgs keeps its size and offsets.
+// How a 32-B record becomes the ray of one sample.  SRC_CALLER (the value of
+// a zero-initialised RaySource) is rt_ray_color: the record is the ray.  The
+// others are rt_gather's sources (1 + rtgpu.h's RT_GATHER_* value): the record
+// is a point and its normal, and the direction is a function of the sample's
+// path key.
+enum : int32_t { SRC_CALLER = 0, SRC_RAY = 1, SRC_COSINE = 2, SRC_SPHERE = 3 };
+
+// The rays of one rt_ray_color / rt_gather range.  A record is two float4
+// (rt_path_ray: origin.xyz, id; direction.xyz, reserved; rt_gather_point has
+// the same layout with the normal as the direction), indexed by the entries of
+// the twin's "pixel list" (WaveArgs::pixels), which name records of this
+// range.  Its own struct, like QueryArgs: WaveArgs keeps its size and offsets.
 struct RaySource {
-  const float4* rays;   // 2 * (rays of the range)
-  uint32_t num_rays;    // rays of the range: every list entry is below it
+  const float4* rays;   // 2 * (records of the range)
+  uint32_t num_rays;    // records of the range: every list entry is below it
+  int32_t kind;         // SRC_*: launch-uniform, it selects the kernel
 };
 
-// Slot i of a batch of `nslots` (= samples * a.npix) takes ray
+// Slot i of a batch of `nslots` (= samples * a.npix) takes record
 // a.pixels[i % a.npix] at sample sample_base + i / a.npix: Lout[i] = 0, and,
-// for a ray that passes the guard, stream 0 gets (origin, slot), (direction,
+// for a record whose ray is valid, stream 0 gets (origin, slot), (direction,
 // key), (1, 1, 1, state(a.max_depth, bounce 0, emitters count)).  The valid
 // rays are dense in stream 0; a.counts[CNT_STREAM0], which must be 0 when the
 // kernel starts (k_set_counts), ends as their number.
@@ -27,5 +37,11 @@ hipError_t launch_ray_source(const WaveArgs& a, const RaySource& src, uint32_t n
 
 // list[k] = k for k < n: the list of a range whose rays are taken in order.
 hipError_t launch_ray_identity(uint32_t* list, uint32_t n, int cus, hipStream_t st);
+
+// rt_gather_rays: out[2k], out[2k+1] = the rt_path_ray that sample `sample` of
+// point k traces under `kind` (SRC_RAY .. SRC_SPHERE) and `seed`, or
+// (p, id), (0, 0, 0, 0) for an invalid point.
+hipError_t launch_gather_rays(const float4* pts, uint32_t n, int32_t kind, uint32_t seed, uint32_t sample, float4* out,
+                              int cus, hipStream_t st);
 
 }  // namespace rtg

@@ -1,6 +1,7 @@
-// ray_source.hip — rt_ray_color's ray source: the caller's rays written as
-// bounce 0's path stream, in front of the unchanged bounce loop of
-// wavefront.hip (run_batches' ray mode).
+// ray_source.hip — the ray sources of rt_ray_color and rt_gather: the caller's
+// rays, or rays drawn per sample from the caller's points, written as bounce
+// 0's path stream, in front of the unchanged bounce loop of wavefront.hip
+// (run_batches' ray mode).
 //
 // A render's bounce 0 has no stream: its kernels regenerate GetRay from the
 // slot index.  Here the rays are data, so k_ray_source writes them out once as
@@ -59,32 +60,75 @@ __device__ __forceinline__ uint32_t lanes_below(unsigned long long m) {
 
 }  // namespace rsrc
 
+// One record under one source kind (ray_source.h's SRC_*) and the sample's
+// path key: is there a ray, and which.  SRC_CALLER: the record is the ray.
+// rt_gather's sources (rtgpu.h): the origin is the point; SRC_RAY's direction
+// is the normal as given, SRC_COSINE's is unit(n) + RandomUnitVector
+// (Lambertian.Scatter's direction, material.go:33-80: density cos/pi about
+// unit(n)) and SRC_SPHERE's is RandomUnitVector alone, drawn at the key's
+// (bounce 0, DOM_SOURCE, 0).  A point with a non-finite component, or, where
+// the normal is read, a normal with one or with a length that len() gives as 0
+// or not finite, has no ray (and draws nothing).  fp32 in the order written.
+// `kind` is launch-uniform: a constant where the caller is a template.
+__device__ __forceinline__ bool source_ray(int kind, float4 o4, float4 d4, uint32_t key, V3& ro, V3& rd) {
+  ro = mk(o4.x, o4.y, o4.z);
+  rd = mk(d4.x, d4.y, d4.z);
+  if (kind == SRC_CALLER) return rsrc::valid_ray(o4, d4);
+  bool ok = rsrc::finite_f(o4.x) && rsrc::finite_f(o4.y) && rsrc::finite_f(o4.z);
+  if (kind != SRC_SPHERE) {
+    const float l = len(rd);
+    ok = ok && rsrc::finite_f(d4.x) && rsrc::finite_f(d4.y) && rsrc::finite_f(d4.z) && l != 0.0f && rsrc::finite_f(l);
+  }
+  if (ok && kind == SRC_COSINE) {
+    const V3 nh = unit(rd);
+    const V3 d = add(nh, random_unit_vector(key, 0u, DOM_SOURCE, 0u));
+    rd = near_zero(d) ? nh : d;
+  }
+  if (ok && kind == SRC_SPHERE) rd = random_unit_vector(key, 0u, DOM_SOURCE, 0u);
+  return ok;
+}
+
 // 256-thread blocks in a grid-stride walk over 256-slot chunks; the trip count
-// is block-uniform, so every thread reaches both barriers of every chunk.
-static __global__ __launch_bounds__(256) void k_ray_source(WaveArgs a, RaySource src, uint32_t nslots, uint32_t sample_base) {
+// is block-uniform, so every thread reaches both barriers of every chunk.  A
+// generated direction (kKind != SRC_CALLER) is complete, rejection loop and
+// all, before the vote: lanes diverge inside source_ray and nowhere else.
+// bdim, gdim: the kernel's blockDim.x and gridDim.x, read in the kernel itself
+// (read here they compile to the non-uniform-block form and k_ray_source's
+// code would change).
+template <int kKind>
+__device__ __forceinline__ void ray_source_chunks(const WaveArgs& a, const RaySource& src, uint32_t nslots, uint32_t sample_base,
+                                                  uint32_t bdim, uint32_t gdim) {
   __shared__ uint32_t s_w[2][4];   // per wave: its valid rays, then their offset in the chunk (double-buffered)
   __shared__ uint32_t s_b[2];      // the chunk's first stream position
-  const uint32_t nchunks = (nslots + blockDim.x - 1u) / blockDim.x;
+  const uint32_t nchunks = (nslots + bdim - 1u) / bdim;
   const int w = int(threadIdx.x >> 6);
   uint32_t par = 0;
-  for (uint32_t c = blockIdx.x; c < nchunks; c += gridDim.x, par ^= 1u) {
-    const uint32_t i = c * blockDim.x + threadIdx.x;
+  for (uint32_t c = blockIdx.x; c < nchunks; c += gdim, par ^= 1u) {
+    const uint32_t i = c * bdim + threadIdx.x;
     bool valid = false;
     float4 o4 = make_float4(0.0f, 0.0f, 0.0f, 0.0f), d4 = o4;
+    uint32_t key = 0u;
     if (i < nslots) {
       const uint32_t ray = a.pixels[i % a.npix];
       rsrc::stnt(&a.Lout[i], make_float4(0.0f, 0.0f, 0.0f, 0.0f));
       if (ray < src.num_rays) {
         o4 = rsrc::ldnt(&src.rays[2u * size_t(ray)]);
         d4 = rsrc::ldnt(&src.rays[2u * size_t(ray) + 1u]);
-        valid = rsrc::valid_ray(o4, d4);
+        if (kKind == SRC_CALLER) {
+          valid = rsrc::valid_ray(o4, d4);
+        } else {   // the ray's origin is the point; its direction takes the normal's place
+          V3 ro, rd;
+          key = path_key(a.seed, __float_as_uint(o4.w), sample_base + i / a.npix);
+          valid = source_ray(kKind, o4, d4, key, ro, rd);
+          d4 = make_float4(rd.x, rd.y, rd.z, d4.w);
+        }
       }
     }
     const unsigned long long m = __ballot(valid);
     if (__lane_id() == 0) s_w[par][w] = uint32_t(__popcll(m));
     __syncthreads();
     if (threadIdx.x == 0) {
-      const int nw = int((blockDim.x + 63u) >> 6);
+      const int nw = int((bdim + 63u) >> 6);
       uint32_t tot = 0;
       for (int k = 0; k < nw; ++k) { const uint32_t n = s_w[par][k]; s_w[par][k] = tot; tot += n; }
       s_b[par] = tot ? atomicAdd(a.counts + CNT_STREAM0, tot) : 0u;
@@ -93,11 +137,39 @@ static __global__ __launch_bounds__(256) void k_ray_source(WaveArgs a, RaySource
     if (valid) {
       // at most nslots valid rays in all: the position is below a.slots
       const uint32_t p = s_b[par] + s_w[par][w] + rsrc::lanes_below(m);
-      const uint32_t key = path_key(a.seed, __float_as_uint(o4.w), sample_base + i / a.npix);
+      if (kKind == SRC_CALLER) key = path_key(a.seed, __float_as_uint(o4.w), sample_base + i / a.npix);
       rsrc::stnt(&a.s[0].o[p], make_float4(o4.x, o4.y, o4.z, __uint_as_float(i)));
       rsrc::stnt(&a.s[0].d[p], make_float4(d4.x, d4.y, d4.z, __uint_as_float(key)));
       rsrc::stnt(&a.s[0].beta[p], make_float4(1.0f, 1.0f, 1.0f, __uint_as_float(rsrc::state0(a.max_depth))));
     }
+  }
+}
+
+// rt_ray_color's source: the caller's rays.
+static __global__ __launch_bounds__(256) void k_ray_source(WaveArgs a, RaySource src, uint32_t nslots, uint32_t sample_base) {
+  ray_source_chunks<SRC_CALLER>(a, src, nslots, sample_base, blockDim.x, gridDim.x);
+}
+
+// rt_gather's sources: one kernel per kind (SRC_RAY, SRC_COSINE, SRC_SPHERE).
+template <int kKind>
+static __global__ __launch_bounds__(256) void k_gather_source(WaveArgs a, RaySource src, uint32_t nslots, uint32_t sample_base) {
+  static_assert(kKind == SRC_RAY || kKind == SRC_COSINE || kKind == SRC_SPHERE, "a gather source");
+  ray_source_chunks<kKind>(a, src, nslots, sample_base, blockDim.x, gridDim.x);
+}
+
+// rt_gather_rays: the ray sample `sample` of every point traces, one point per
+// thread and trip: two 16-B loads, two 16-B stores, neighbours adjacent.
+static __global__ __launch_bounds__(256) void k_gather_rays(const float4* pts, uint32_t n, int kind, uint32_t seed,
+                                                            uint32_t sample, float4* out) {
+  const uint32_t gs = gridDim.x * blockDim.x;
+  for (uint32_t k = blockIdx.x * blockDim.x + threadIdx.x; k < n; k += gs) {
+    const float4 o4 = rsrc::ldnt(&pts[2u * size_t(k)]);
+    const float4 d4 = rsrc::ldnt(&pts[2u * size_t(k) + 1u]);
+    V3 ro, rd;
+    const bool valid = source_ray(kind, o4, d4, path_key(seed, __float_as_uint(o4.w), sample), ro, rd);
+    if (!valid) rd = mk(0.0f, 0.0f, 0.0f);
+    rsrc::stnt(&out[2u * size_t(k)], o4);   // (p, id) as given, so rt_ray_color's guard sees what this one saw
+    rsrc::stnt(&out[2u * size_t(k) + 1u], make_float4(rd.x, rd.y, rd.z, __uint_as_float(0u)));
   }
 }
 
@@ -122,8 +194,24 @@ hipError_t launch_ray_source(const WaveArgs& a, const RaySource& src, uint32_t n
   if (!src.rays || a.npix == 0 || nslots > a.slots || nslots % a.npix != 0) return hipErrorInvalidValue;
   // memory-bound and short: a few blocks per CU cover the latency, and never more than one per chunk
   const long long need = (nslots + 255u) / 256u, resident = (long long)(cus > 0 ? cus : 1) * 8;
-  hipLaunchKernelGGL(k_ray_source, dim3(uint32_t(need < resident ? need : resident)), dim3(256), 0, st, a, src, nslots,
-                     sample_base);
+  const dim3 grid(uint32_t(need < resident ? need : resident)), block(256);
+  switch (src.kind) {
+    case SRC_CALLER: hipLaunchKernelGGL(k_ray_source, grid, block, 0, st, a, src, nslots, sample_base); break;
+    case SRC_RAY: hipLaunchKernelGGL(k_gather_source<SRC_RAY>, grid, block, 0, st, a, src, nslots, sample_base); break;
+    case SRC_COSINE: hipLaunchKernelGGL(k_gather_source<SRC_COSINE>, grid, block, 0, st, a, src, nslots, sample_base); break;
+    case SRC_SPHERE: hipLaunchKernelGGL(k_gather_source<SRC_SPHERE>, grid, block, 0, st, a, src, nslots, sample_base); break;
+    default: return hipErrorInvalidValue;   // a missing kernel is an error
+  }
+  return hipGetLastError();
+}
+
+hipError_t launch_gather_rays(const float4* pts, uint32_t n, int32_t kind, uint32_t seed, uint32_t sample, float4* out,
+                              int cus, hipStream_t st) {
+  if (n == 0) return hipSuccess;
+  if (!pts || !out || kind < SRC_RAY || kind > SRC_SPHERE) return hipErrorInvalidValue;
+  const long long need = (n + 255u) / 256u, resident = (long long)(cus > 0 ? cus : 1) * 8;
+  hipLaunchKernelGGL(k_gather_rays, dim3(uint32_t(need < resident ? need : resident)), dim3(256), 0, st, pts, n, int(kind),
+                     seed, sample, out);
   return hipGetLastError();
 }
 #endif  // RTG_HOST_EMU

@@ -913,8 +913,67 @@ func (c *Ctx) RayColor(rays []PathRay, p RayColorParams, rgb []float32) (RayColo
 	return st, c.check(rc)
 }
 
+// Direction sources of Gather.
+const (
+	GatherRay    int32 = 0 // RT_GATHER_RAY
+	GatherCosine int32 = 1 // RT_GATHER_COSINE
+	GatherSphere int32 = 2 // RT_GATHER_SPHERE
+)
+
+// GatherPoint mirrors rt_gather_point (PathRay's layout): a position, the
+// pixel word of its RNG key, and a normal that need not be unit.  Reserved
+// must be 0.
+//
+//rtgpu:mirror rt_gather_point
+type GatherPoint struct {
+	P        [3]float32 `c:"p"`
+	ID       uint32     `c:"id"`
+	N        [3]float32 `c:"n"`
+	Reserved uint32     `c:"reserved"`
+}
+
+// GatherParams mirrors rt_gather_params.  Path holds the words of a
+// RayColorParams (56 B, 8-aligned); Gather fills it.
+//
+//rtgpu:mirror rt_gather_params
+type GatherParams struct {
+	Path     [7]uint64 `c:"path"`
+	Source   int32     `c:"source"`
+	Reserved int32     `c:"reserved"`
+}
+
+// Gather is RayColor over directions drawn on the device (rt_gather): sample s
+// of point i starts at pts[i].P under the key (p.Seed, pts[i].ID,
+// p.SampleOffset + s) along pts[i].N (GatherRay), along unit(N) plus a random
+// unit vector (GatherCosine: density cos/pi about the normal, so the
+// irradiance is pi * rgb / samples), or along a random unit vector
+// (GatherSphere: the mean over the sphere is rgb / samples).  Everything else
+// is RayColor's.  A point with a non-finite component, or a normal of length 0
+// or not finite where it is read, adds nothing and is counted in the stats.
+// Blocks.
+func (c *Ctx) Gather(pts []GatherPoint, source int32, p RayColorParams, rgb []float32) (RayColorStats, error) {
+	var st RayColorStats
+	if len(rgb) < 3*len(pts) {
+		return st, &Error{StatusInvalid, "radiance buffer too small"}
+	}
+	if len(pts) == 0 {
+		return st, nil
+	}
+	var gp GatherParams
+	*(*RayColorParams)(unsafe.Pointer(&gp.Path)) = p
+	gp.Source = source
+	rc := C.rt_gather(c.p, (*C.rt_gather_point)(unsafe.Pointer(&pts[0])), C.int64_t(len(pts)),
+		(*C.rt_gather_params)(unsafe.Pointer(&gp)), (*C.float)(unsafe.Pointer(&rgb[0])),
+		(*C.rt_ray_color_stats)(unsafe.Pointer(&st)))
+	return st, c.check(rc)
+}
+
 // Layout checks: each mirror is exactly as large as its C struct.
 var (
+	_ [unsafe.Sizeof(GatherPoint{}) - uintptr(C.sizeof_rt_gather_point)]byte
+	_ [uintptr(C.sizeof_rt_gather_point) - unsafe.Sizeof(GatherPoint{})]byte
+	_ [unsafe.Sizeof(GatherParams{}) - uintptr(C.sizeof_rt_gather_params)]byte
+	_ [uintptr(C.sizeof_rt_gather_params) - unsafe.Sizeof(GatherParams{})]byte
 	_ [unsafe.Sizeof(PathRay{}) - uintptr(C.sizeof_rt_path_ray)]byte
 	_ [uintptr(C.sizeof_rt_path_ray) - unsafe.Sizeof(PathRay{})]byte
 	_ [unsafe.Sizeof(RayColorParams{}) - uintptr(C.sizeof_rt_ray_color_params)]byte

@@ -951,6 +951,69 @@ int rt_ray_color(rt_ctx* ctx, const rt_path_ray* rays, int64_t n, const rt_ray_c
 int rt_ray_color_device(rt_ctx* ctx, const rt_path_ray* rays_dev, int64_t n, const rt_ray_color_params* params,
                         float* rgb_dev, void* hip_stream);
 
+/* ---- Gathers: path integrals over directions drawn on the device -----------
+ * How much light arrives at this point?  (Irradiance and lightmap bakes,
+ * light probes, ambient gathers: INTEGRATION.md §4.)  rt_ray_color with a new
+ * direction for every sample of every point, drawn on the device from a 32-B
+ * record per point, so nothing per sample crosses the bus.
+ *
+ * Result: rgb[3*i .. 3*i+2] is the sum, over path.samples samples, of
+ * rayColorInternal(ray_{i,s}, max_depth).  Everything rt_ray_color documents
+ * holds unchanged: the fp64 per-point sum in sample order rounded once,
+ * accumulate, the cut of the array into ranges, the independence of the
+ * schedule options, volumes, the ray time from the key's camera draw 2, the
+ * first device of a multi-device context, how errors surface, the limits on n
+ * and n == 0.
+ *
+ * Only the ray of sample s is new.  Its key is path_key(seed, pts[i].id,
+ * sample_offset + s), its origin is p, and its direction d comes from `source`,
+ * in fp32 in the order written with no fused multiply-add:
+ *   RT_GATHER_RAY     d = n, as given.  The call is rt_ray_color on the same
+ *                     32 bytes, bit for bit (for every point valid here).
+ *   RT_GATHER_COSINE  nh = unit(n); u = random_unit_vector(key, bounce 0,
+ *                     DOM_SOURCE = 7, index 0); d = nh + u, and d = nh where
+ *                     near_zero(d).  Lambertian.Scatter's direction
+ *                     (material.go:33-80): density cos(theta)/pi about nh, so
+ *                     the irradiance at the point is pi * rgb / samples.
+ *   RT_GATHER_SPHERE  d = random_unit_vector(key, 0, DOM_SOURCE, 0); n is not
+ *                     read.  The mean over the sphere is rgb / samples.
+ * The path's own draws (camera 2, scatter, NEE, volumes) keep their addresses.
+ * After 64 rejected tries random_unit_vector returns (0,0,1).
+ *
+ * A point is invalid when a component of p is non-finite, and, for RAY and
+ * COSINE, when a component of n is non-finite or n's fp32 length
+ * sqrtf(x*x + y*y + z*z) is 0 or not finite (so a normal whose squared length
+ * leaves fp32's range is invalid even for RAY).  An invalid point traces
+ * nothing, adds (0,0,0), raises no device error, and is counted in
+ * stats->invalid_rays (host variant only).
+ *
+ * rt_gather_rays is the probe: out[i] is the rt_path_ray that sample `sample`
+ * (the index itself: sample_offset + s) of point i traces, and
+ * {p, id, (0,0,0), 0} for an invalid point, which rt_ray_color treats as
+ * invalid too.  The equality that defines rt_gather: rt_ray_color over
+ * rt_gather_rays(.., s) with samples = 1, sample_offset = s is rt_gather with
+ * samples = 1, sample_offset = s, bit for bit.  It needs no uploaded scene,
+ * blocks, and stages through buffers the context owns.
+ *
+ * RT_ERR_INVALID: everything rt_ray_color refuses, a source outside 0..2, a
+ * non-zero params->reserved, a point's reserved != 0 (host variant only), and
+ * for rt_gather_rays sample < 0.
+ * Not offered (yet): next-event estimation at the gather point itself (direct
+ * light reaches a point only through rays that hit an emitter, as for a camera
+ * ray), SH projection of a probe, moments or adaptive sampling over points,
+ * per-point source kinds.                                                     */
+enum { RT_GATHER_RAY = 0, RT_GATHER_COSINE = 1, RT_GATHER_SPHERE = 2 };
+typedef struct rt_gather_point { float p[3]; uint32_t id; float n[3]; uint32_t reserved; } rt_gather_point; /* 32 B, rt_path_ray's layout */
+typedef struct rt_gather_params { rt_ray_color_params path; int32_t source; int32_t reserved; } rt_gather_params; /* 64 B */
+
+int rt_gather(rt_ctx* ctx, const rt_gather_point* pts, int64_t n, const rt_gather_params* params, float* rgb,
+              rt_ray_color_stats* stats /* may be NULL */);
+int rt_gather_device(rt_ctx* ctx, const rt_gather_point* pts_dev, int64_t n, const rt_gather_params* params,
+                     float* rgb_dev, void* hip_stream);
+/* probe: the ray sample `sample` of every point traces */
+int rt_gather_rays(rt_ctx* ctx, const rt_gather_point* pts, int64_t n, int32_t source, uint32_t seed, int32_t sample,
+                   rt_path_ray* out);
+
 #ifdef __cplusplus
 }
 #endif
