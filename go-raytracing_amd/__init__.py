@@ -268,6 +268,23 @@ def gather_params(source: int, samples: int, depth: int, seed: int = 1, sample_o
     return g
 
 
+RT_SH_MAX_BANDS = 3
+
+
+class RtGatherShParams(C.Structure):
+    """rt_gather_sh_params (64 B, rt_gather_params' layout)."""
+    _fields_ = [("path", RtRayColorParams), ("bands", C.c_int32), ("reserved", C.c_int32)]
+
+
+def gather_sh_params(bands: int, samples: int, depth: int, seed: int = 1, sample_offset: int = 0, camera=None,
+                     accumulate: bool = False, **sky) -> RtGatherShParams:
+    """rt_gather_sh_params: `bands` (1..3) and the path fields of ray_color_params."""
+    g = RtGatherShParams()
+    g.path = ray_color_params(samples, depth, seed, sample_offset, camera, accumulate, **sky)
+    g.bands = bands
+    return g
+
+
 class RtWorkCounts(C.Structure):
     _fields_ = [(n, C.c_uint64) for n in ("samples", "rays", "shadow_rays", "node_visits", "sphere_tests",
                                           "quad_tests", "tri_tests", "plane_tests", "instance_visits",
@@ -406,6 +423,10 @@ def rtgpu() -> C.CDLL:
                                       C.POINTER(C.c_float), C.POINTER(RtRayColorStats)]
             lib.rt_gather_device.argtypes = [P, P, C.c_int64, C.POINTER(RtGatherParams), P, P]
             lib.rt_gather_rays.argtypes = [P, C.POINTER(RtGatherPoint), C.c_int64, I32, U32, I32, C.POINTER(RtPathRay)]
+        if hasattr(lib, "rt_gather_sh"):
+            lib.rt_gather_sh.argtypes = [P, C.POINTER(RtGatherPoint), C.c_int64, C.POINTER(RtGatherShParams),
+                                         C.POINTER(C.c_float), C.POINTER(RtRayColorStats)]
+            lib.rt_gather_sh_device.argtypes = [P, P, C.c_int64, C.POINTER(RtGatherShParams), P, P]
         _rtgpu = lib
     return _rtgpu
 
@@ -1134,6 +1155,33 @@ class Context:
         self._check(self._lib.rt_gather_rays(self._h, pts.ctypes.data_as(C.POINTER(RtGatherPoint)), pts.shape[0], source,
                                              seed, sample, out.ctypes.data_as(C.POINTER(RtPathRay))))
         return out
+
+    # ---- SH projection of a probe (rt_gather_sh)
+    def gather_sh(self, pts: np.ndarray, bands: int, samples: int, depth: int, seed: int = 1, sample_offset: int = 0,
+                  camera=None, accum: Optional[np.ndarray] = None, **sky):
+        """rt_gather_sh: pts as for gather (n is not read); returns the
+        (n, bands^2, 3) float32 sums over `samples` directions on the sphere of
+        radiance times the real SH basis at the direction, and the stats.  The
+        projection coefficients are 4 pi / samples times the sums.  accum: sums
+        of earlier calls to add to.  The rest as gather."""
+        pts = np.ascontiguousarray(pts, GATHER_POINT_DTYPE)
+        n = pts.shape[0]
+        p = gather_sh_params(bands, samples, depth, seed, sample_offset, camera, accum is not None, **sky)
+        k = bands * bands if 1 <= bands <= RT_SH_MAX_BANDS else 1          # (the call refuses other bands)
+        if accum is None:
+            accum = np.zeros((n, k, 3), np.float32)
+        if accum.dtype != np.float32 or accum.size != 3 * k * n or not accum.flags["C_CONTIGUOUS"]:
+            raise ValueError("accum must be a contiguous float32 array of 3 * bands^2 floats per point")
+        st = RtRayColorStats()
+        self._check(self._lib.rt_gather_sh(self._h, pts.ctypes.data_as(C.POINTER(RtGatherPoint)), n, C.byref(p),
+                                           _f32p(accum), C.byref(st)))
+        return accum.reshape(n, k, 3), st
+
+    def gather_sh_device(self, pts_ptr: int, n: int, params: RtGatherShParams, sh_ptr: int, stream: int = 0):
+        """rt_gather_sh_device: n rt_gather_point at device address pts_ptr ->
+        3 * bands^2 * n floats at sh_ptr, asynchronous on `stream`."""
+        self._check(self._lib.rt_gather_sh_device(self._h, C.c_void_p(pts_ptr), n, C.byref(params), C.c_void_p(sh_ptr),
+                                                  C.c_void_p(stream)))
 
 
 # ---------------------------------------------------------------------------

@@ -141,6 +141,8 @@ struct rt_ctx {
   // rc_ev follows the latest call's work on rc_st, so a call on another stream
   // starts after it (they share the batch buffers)
   DevBuf rc_rays, rc_rgb;
+  // rt_gather_sh (RenderRun::sh_bands): 3 * bands^2 fp64 sums per listed point
+  DevBuf wshacc;
   hipEvent_t rc_ev = nullptr;
   hipStream_t rc_st = nullptr;
   bool rc_pending = false;
@@ -354,6 +356,9 @@ struct RenderRun {
   // rt_ray_color (WavePlan::ray_src; with from_list): the list's entries name
   // rays of `rays`, bounce 0 traces those, and `d_out` holds 3 floats per ray
   const RaySource* rays = nullptr;
+  // rt_gather_sh (WavePlan::sh_acc; with rays under SRC_SPHERE): `d_out` holds
+  // 3 * sh_bands^2 floats per point in the rgb sums' place
+  int sh_bands = 0;
 };
 
 // LDS stack ring (kLdsStack entries per lane) + global spill up to
@@ -416,7 +421,7 @@ int guard_render_report(rt_ctx* ctx, int nt) {
   if (gr[0]) fprintf(stderr, "RTG_GUARD: %u bad indices, first at site %u: index %u >= length %u\n", gr[0], gr[1], gr[2], gr[3]);
   const struct { const char* name; const DevBuf* b; } bufs[] = {
       {"wstate", &ctx->wstate}, {"wq", &ctx->wq}, {"wpix", &ctx->wpix}, {"wacc", &ctx->wacc}, {"wfacc", &ctx->wfacc},
-      {"wmacc", &ctx->wmacc},
+      {"wmacc", &ctx->wmacc}, {"wshacc", &ctx->wshacc},
       {"wspill", &ctx->wspill}, {"counters", &ctx->counters}, {"accum", &ctx->accum}, {"frame", &ctx->frame}};
   for (const auto& x : bufs)
     if (const size_t bad = canary_damage(*x.b))
@@ -485,6 +490,7 @@ int render_wave(rt_ctx* ctx, const DCamera& dc, const rt_render_params* p, const
   if ((rc = ensure(ctx, ctx->wacc, size_t(npix) * 3 * sizeof(double)))) return rc;
   if (run.feat && (rc = ensure(ctx, ctx->wfacc, size_t(npix) * kFeatFloats * sizeof(double)))) return rc;
   if (run.mom_out && (rc = ensure(ctx, ctx->wmacc, size_t(npix) * kMomFloats * sizeof(double)))) return rc;
+  if (run.sh_bands && (rc = ensure(ctx, ctx->wshacc, size_t(npix) * sh_floats(run.sh_bands) * sizeof(double)))) return rc;
   if ((rc = ensure(ctx, ctx->counters, CNT_WORDS * sizeof(unsigned long long)))) return rc;
   if ((rc = ensure(ctx, ctx->wspill, spill.words() * sizeof(uint32_t)))) return rc;
   if (!run.from_list && (rc = stage_pixels(ctx, st))) return rc;
@@ -498,6 +504,7 @@ int render_wave(rt_ctx* ctx, const DCamera& dc, const rt_render_params* p, const
   cap.pix = std::min(ctx->wpix.bytes / sizeof(uint32_t), ctx->wacc.bytes / (3 * sizeof(double)));
   if (run.feat) cap.pix = std::min(cap.pix, ctx->wfacc.bytes / (kFeatFloats * sizeof(double)));
   if (run.mom_out) cap.pix = std::min(cap.pix, ctx->wmacc.bytes / (kMomFloats * sizeof(double)));
+  if (run.sh_bands) cap.pix = std::min(cap.pix, ctx->wshacc.bytes / (sh_floats(run.sh_bands) * sizeof(double)));
   cap.spill = ctx->wspill.bytes / sizeof(uint32_t);
   const WaveLayout lay = slice_twins(bs.spb, twin_npix, nt, lit, overlap, spill, cap);
   if (!check(lay))
@@ -505,6 +512,7 @@ int render_wave(rt_ctx* ctx, const DCamera& dc, const rt_render_params* p, const
   WaveArgs as[kMaxTwins]{};
   double* feat_acc[kMaxTwins] = {};   // feature mode: each twin's slice of wfacc
   double* mom_acc[kMaxTwins] = {};    // moments mode: each twin's slice of wmacc
+  double* sh_acc[kMaxTwins] = {};     // SH mode: each twin's slice of wshacc (coefficient-major within the twin)
   hipStream_t sts[kMaxTwins] = {st};
   for (int t = 1; t < kMaxTwins; ++t) sts[t] = ctx->twin_st[t - 1];
   for (int t = 0; t < nt; ++t) {
@@ -514,6 +522,7 @@ int render_wave(rt_ctx* ctx, const DCamera& dc, const rt_render_params* p, const
               static_cast<uint32_t*>(ctx->wspill.p), lay.tw[t], lit);
     if (run.feat) feat_acc[t] = static_cast<double*>(ctx->wfacc.p) + lay.tw[t].pix_off * kFeatFloats;
     if (run.mom_out) mom_acc[t] = static_cast<double*>(ctx->wmacc.p) + lay.tw[t].pix_off * kMomFloats;
+    if (run.sh_bands) sh_acc[t] = static_cast<double*>(ctx->wshacc.p) + lay.tw[t].pix_off * sh_floats(run.sh_bands);
     a.seed = p->seed;
     a.max_depth = p->max_depth;
     a.counters = static_cast<unsigned long long*>(ctx->counters.p);
@@ -541,6 +550,11 @@ int render_wave(rt_ctx* ctx, const DCamera& dc, const rt_render_params* p, const
     plan.mom_out = run.mom_out;
   }
   plan.ray_src = run.rays;
+  if (run.sh_bands) {
+    plan.sh_acc = sh_acc;
+    plan.sh_out = d_out;
+    plan.sh_bands = run.sh_bands;
+  }
   plan.num_cus = ctx->num_cus;
   plan.max_blocks = knobs.max_blocks;
   plan.num_twins = nt;
@@ -868,6 +882,7 @@ void rt_ctx_destroy(rt_ctx* ctx) {
   free_buf(ctx->wfacc); free_buf(ctx->feat);
   free_buf(ctx->dn_work); free_buf(ctx->dn_in); free_buf(ctx->dn_feat); free_buf(ctx->dn_out);
   free_buf(ctx->wmacc); free_buf(ctx->mom);
+  free_buf(ctx->wshacc);
   free_buf(ctx->dv_work); free_buf(ctx->dv_mom); free_buf(ctx->dv_var);
   free_buf(ctx->ad_work); free_buf(ctx->ad_counts);
   if (ctx->ad_pinned) (void)hipHostFree(ctx->ad_pinned);
@@ -2220,8 +2235,11 @@ int ray_color_check(rt_ctx* ctx, const rt_ray_color_params* p, int64_t n, DCamer
 // list (ray k of the range -> rgb[3k]), with all its samples, so a ray's sum
 // never depends on the cut.  kind (ray_source.h's SRC_*): the records are rays
 // (rt_ray_color) or rt_gather's points under one of its sources.
+// sh_bands > 0 (rt_gather_sh; kind is SRC_SPHERE): `rgb` holds 3 * sh_bands^2
+// floats per point, the SH sums, in the rgb sums' place.
 int ray_color_device(rt_ctx* ctx, const DCamera& dc, int32_t kind, const rt_path_ray* rays, int64_t n,
-                     const rt_ray_color_params* p, float* rgb, hipStream_t st) {
+                     const rt_ray_color_params* p, float* rgb, hipStream_t st, int sh_bands = 0) {
+  const size_t stride = sh_bands ? size_t(sh_floats(sh_bands)) : 3;   // floats per record of the output
   const bool lit = ctx->dscene.num_lights > 0;
   const WaveKnobs knobs = resolve_knobs(ctx->wopt, false);
   size_t target = knobs.slots;
@@ -2254,7 +2272,8 @@ int ray_color_device(rt_ctx* ctx, const DCamera& dc, int32_t kind, const rt_path
     run.from_list = true;
     run.list_n = src.num_rays;
     run.rays = &src;
-    if ((rc = render_wave(ctx, dc, &q, none, rgb + 3 * off, run))) return rc;
+    run.sh_bands = sh_bands;
+    if ((rc = render_wave(ctx, dc, &q, none, rgb + stride * size_t(off), run))) return rc;
   }
   HIPCHK(hipEventRecord(ctx->rc_ev, st));
   ctx->rc_st = st;
@@ -2266,21 +2285,22 @@ int ray_color_device(rt_ctx* ctx, const DCamera& dc, int32_t kind, const rt_path
 // points: the same 32 B) staged through the context's buffers, traced, copied
 // back; blocks.  invalid: the records the kernel's guard will leave out.
 int ray_color_host(rt_ctx* ctx, const DCamera& dc, int32_t kind, const void* recs, int64_t n, const rt_ray_color_params* params,
-                   float* rgb, rt_ray_color_stats* stats, uint64_t invalid) {
+                   float* rgb, rt_ray_color_stats* stats, uint64_t invalid, int sh_bands = 0) {
+  const size_t out_bytes = size_t(n) * (sh_bands ? size_t(sh_floats(sh_bands)) : 3) * sizeof(float);
   int rc = check_render_error(ctx, true);
   if (rc) return rc;
   double ms = 0.0;
   if (n > 0) {
     hipStream_t st = ctx->stream;
     if ((rc = ensure(ctx, ctx->rc_rays, size_t(n) * sizeof(rt_path_ray)))) return rc;
-    if ((rc = ensure(ctx, ctx->rc_rgb, size_t(n) * 3 * sizeof(float)))) return rc;
+    if ((rc = ensure(ctx, ctx->rc_rgb, out_bytes))) return rc;
     HIPCHK(hipMemcpyAsync(ctx->rc_rays.p, recs, size_t(n) * sizeof(rt_path_ray), hipMemcpyHostToDevice, st));
     if (params->accumulate)
-      HIPCHK(hipMemcpyAsync(ctx->rc_rgb.p, rgb, size_t(n) * 3 * sizeof(float), hipMemcpyHostToDevice, st));
+      HIPCHK(hipMemcpyAsync(ctx->rc_rgb.p, rgb, out_bytes, hipMemcpyHostToDevice, st));
     if ((rc = ray_color_device(ctx, dc, kind, static_cast<const rt_path_ray*>(ctx->rc_rays.p), n, params,
-                               static_cast<float*>(ctx->rc_rgb.p), st)))
+                               static_cast<float*>(ctx->rc_rgb.p), st, sh_bands)))
       return rc;
-    HIPCHK(hipMemcpyAsync(rgb, ctx->rc_rgb.p, size_t(n) * 3 * sizeof(float), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(rgb, ctx->rc_rgb.p, out_bytes, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
     if ((rc = check_render_error(ctx, true))) return rc;
     float f = 0.f;
@@ -2299,6 +2319,13 @@ int ray_color_host(rt_ctx* ctx, const DCamera& dc, int32_t kind, const void* rec
 int gather_check(rt_ctx* ctx, int32_t source, int32_t reserved) {
   if (source < RT_GATHER_RAY || source > RT_GATHER_SPHERE) return set_err(ctx, RT_ERR_INVALID, "gather source outside 0 .. 2");
   if (reserved != 0) return set_err(ctx, RT_ERR_INVALID, "rt_gather_params.reserved is not 0");
+  return RT_OK;
+}
+
+// rt_gather_sh's own refusals (the rest are ray_color_check's).
+int gather_sh_check(rt_ctx* ctx, int32_t bands, int32_t reserved) {
+  if (bands < 1 || bands > RT_SH_MAX_BANDS) return set_err(ctx, RT_ERR_INVALID, "SH bands outside 1 .. 3");
+  if (reserved != 0) return set_err(ctx, RT_ERR_INVALID, "rt_gather_sh_params.reserved is not 0");
   return RT_OK;
 }
 
@@ -2424,6 +2451,40 @@ int rt_gather_rays(rt_ctx* ctx, const rt_gather_point* pts, int64_t n, int32_t s
   HIPCHK(hipMemcpyAsync(out, ctx->rc_rgb.p, bytes, hipMemcpyDeviceToHost, st));
   HIPCHK(hipStreamSynchronize(st));
   return RT_OK;
+}
+
+// ---- rt_gather_sh: rt_gather over the sphere, projected by k_sh_accum --------
+
+static_assert(sizeof(rt_gather_sh_params) == sizeof(rt_gather_params) && RT_SH_MAX_BANDS == kShMaxBands,
+              "rt_gather_sh_params is rt_gather_params' layout");
+
+int rt_gather_sh(rt_ctx* ctx, const rt_gather_point* pts, int64_t n, const rt_gather_sh_params* params, float* sh,
+                 rt_ray_color_stats* stats) {
+  if (!ctx || !pts || !params || !sh) return RT_ERR_INVALID;
+  HIPCHK(hipSetDevice(ctx->device));
+  if (int rc = gather_sh_check(ctx, params->bands, params->reserved)) return rc;
+  DCamera dc{};
+  int rc = ray_color_check(ctx, &params->path, n, dc);
+  if (rc) return rc;
+  uint64_t invalid = 0;
+  for (int64_t i = 0; i < n; ++i) {
+    if (pts[i].reserved != 0) return set_err(ctx, RT_ERR_INVALID, "a point's reserved word is not 0");
+    invalid += !gather_point_valid(pts[i], RT_GATHER_SPHERE);
+  }
+  return ray_color_host(ctx, dc, SRC_SPHERE, pts, n, &params->path, sh, stats, invalid, params->bands);
+}
+
+int rt_gather_sh_device(rt_ctx* ctx, const rt_gather_point* pts_dev, int64_t n, const rt_gather_sh_params* params,
+                        float* sh_dev, void* hip_stream) {
+  if (!ctx || !pts_dev || !params || !sh_dev) return RT_ERR_INVALID;
+  HIPCHK(hipSetDevice(ctx->device));
+  hipStream_t st = hip_stream ? static_cast<hipStream_t>(hip_stream) : ctx->stream;
+  if (int rc = gather_sh_check(ctx, params->bands, params->reserved)) return rc;
+  DCamera dc{};
+  int rc = ray_color_check(ctx, &params->path, n, dc);
+  if (rc || (rc = check_render_error(ctx, false)) || n == 0) return rc;
+  return ray_color_device(ctx, dc, SRC_SPHERE, reinterpret_cast<const rt_path_ray*>(pts_dev), n, &params->path, sh_dev, st,
+                          params->bands);
 }
 
 }  // extern "C"

@@ -1,6 +1,6 @@
 // ray_source.h — launch interface of ray_source.hip: the caller's rays, or rays
 // drawn on the device from the caller's points, as bounce 0 of the wavefront
-// pipeline (rt_ray_color, rt_gather).
+// pipeline (rt_ray_color, rt_gather), and rt_gather_sh's SH projection behind it.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -43,5 +43,20 @@ hipError_t launch_ray_identity(uint32_t* list, uint32_t n, int cus, hipStream_t 
 // (p, id), (0, 0, 0, 0) for an invalid point.
 hipError_t launch_gather_rays(const float4* pts, uint32_t n, int32_t kind, uint32_t seed, uint32_t sample, float4* out,
                               int cus, hipStream_t st);
+
+// rt_gather_sh (WavePlan::sh_acc): the sums of one point, 3 per coefficient.
+constexpr int kShMaxBands = 3;   // rtgpu.h's RT_SH_MAX_BANDS
+constexpr int sh_floats(int bands) { return 3 * bands * bands; }
+
+// After a batch's k_accum: acc[(k * 3 + c) * a.npix + pi] += sum over the
+// batch's nsamp samples q, in that order, of double(Lout[q * a.npix + pi].c) *
+// double(Y_k(d)), d the SRC_SPHERE direction of record a.pixels[pi] at sample
+// sample_base + q, for k < bands^2.  src.kind must be SRC_SPHERE.  An invalid
+// point's sums are left as they are.
+hipError_t launch_sh_accum(const WaveArgs& a, const RaySource& src, uint32_t nsamp, uint32_t sample_base, int bands,
+                           double* acc, int cus, hipStream_t st);
+// out[pixels[pi] * 3 bands^2 + j] = float(acc[j * npix + pi] (+ out with `accumulate`)) (as k_finalize).
+hipError_t launch_sh_finalize(const double* acc, const uint32_t* pixels, uint32_t npix, int bands, float* out,
+                              int accumulate, int cus, hipStream_t st);
 
 }  // namespace rtg

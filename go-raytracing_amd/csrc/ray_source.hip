@@ -15,7 +15,8 @@
 // one atomic each (block_reserve2's scheme, one queue), so the stream follows
 // the caller's ray order chunk by chunk and the XCD claim segments of
 // k_extend see neighbouring rays together.  Stream order never changes a
-// result.
+// result.  Behind the bounce loop, rt_gather_sh's projection of the finished
+// radiances onto the SH basis (k_sh_accum, k_sh_finalize, below).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "dev_layout.h"
@@ -173,6 +174,92 @@ static __global__ __launch_bounds__(256) void k_gather_rays(const float4* pts, u
   }
 }
 
+// ---- rt_gather_sh: the SH projection of a probe (rtgpu.h) -------------------
+// The render is rt_gather's under SRC_SPHERE, untouched.  After a batch's last
+// bounce k_sh_accum reads the Lout entries k_accum reads, in k_accum's order,
+// and weights each sample's radiance with the SH basis at the sample's
+// direction, which it draws again from the key through source_ray: the path
+// streams carry no bounce-0 direction and gain none.  One listed point per
+// lane: per point one 16-B load of the record's first half (p, id) and
+// 3 * kBands^2 fp64 sums in registers over the sample loop (kBands is a
+// template parameter so that one band does not carry nine bands' registers);
+// per sample one coalesced 16-B load of Lout, one direction and 3 * kBands^2
+// fp64 multiply-adds (the product of two floats is exact in fp64).  The sums
+// live between batches in acc[(k * 3 + c) * npix + pi], coefficient-major, so
+// the lanes of a wave load and store adjacent doubles.  An invalid point is
+// skipped before any draw: its sums stay 0.
+namespace shp {
+
+// The basis of rtgpu.h in fp32, in the order written (-ffp-contract=off).
+template <int kBands>
+__device__ __forceinline__ void basis(V3 d, float (&Y)[kBands * kBands]) {
+  const float x = d.x, y = d.y, z = d.z;
+  Y[0] = 0.282095f;
+  if constexpr (kBands >= 2) {
+    Y[1] = 0.488603f * y;
+    Y[2] = 0.488603f * z;
+    Y[3] = 0.488603f * x;
+  }
+  if constexpr (kBands >= 3) {
+    Y[4] = 1.092548f * (x * y);
+    Y[5] = 1.092548f * (y * z);
+    Y[6] = 0.315392f * (3.0f * (z * z) - 1.0f);
+    Y[7] = 1.092548f * (x * z);
+    Y[8] = 0.546274f * (x * x - y * y);
+  }
+}
+
+}  // namespace shp
+
+template <int kBands>
+static __global__ __launch_bounds__(256) void k_sh_accum(const float4* Lout, const uint32_t* pixels, RaySource src,
+                                                         uint32_t npix, uint32_t nsamp, uint32_t seed, uint32_t sample_base,
+                                                         double* acc) {
+  static_assert(kBands >= 1 && kBands <= 3, "rtgpu.h's RT_SH_MAX_BANDS");
+  constexpr int K = kBands * kBands;
+  const uint32_t gs = gridDim.x * blockDim.x;
+  for (uint32_t pi = blockIdx.x * blockDim.x + threadIdx.x; pi < npix; pi += gs) {
+    const uint32_t ray = pixels[pi];
+    if (ray >= src.num_rays) continue;
+    const float4 o4 = rsrc::ldnt(&src.rays[2u * size_t(ray)]);
+    if (!(rsrc::finite_f(o4.x) && rsrc::finite_f(o4.y) && rsrc::finite_f(o4.z))) continue;   // source_ray's guard, before any draw
+    double a[K * 3];
+#pragma unroll
+    for (int j = 0; j < K * 3; ++j) a[j] = acc[size_t(j) * npix + pi];
+    for (uint32_t s = 0; s < nsamp; ++s) {
+      const float4 L = Lout[size_t(s) * npix + pi];
+      V3 ro, rd;
+      source_ray(SRC_SPHERE, o4, o4, path_key(seed, __float_as_uint(o4.w), sample_base + s), ro, rd);   // n is not read
+      float Y[K];
+      shp::basis<kBands>(rd, Y);
+#pragma unroll
+      for (int k = 0; k < K; ++k) {
+        const double y = double(Y[k]);
+        a[k * 3] += double(L.x) * y;
+        a[k * 3 + 1] += double(L.y) * y;
+        a[k * 3 + 2] += double(L.z) * y;
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < K * 3; ++j) acc[size_t(j) * npix + pi] = a[j];
+  }
+}
+
+// out[pixels[pi] * nc + j] = float(acc[j * npix + pi] (+ out with `accumulate`))
+// for the nc = 3 * bands^2 sums of each listed point (k_finalize's expression).
+static __global__ __launch_bounds__(256) void k_sh_finalize(const double* acc, const uint32_t* pixels, uint32_t npix,
+                                                            uint32_t nc, float* out, int accumulate) {
+  const uint32_t gs = gridDim.x * blockDim.x;
+  for (uint32_t pi = blockIdx.x * blockDim.x + threadIdx.x; pi < npix; pi += gs) {
+    float* o = out + size_t(pixels[pi]) * nc;
+    for (uint32_t j = 0; j < nc; ++j) {
+      double v = acc[size_t(j) * npix + pi];
+      if (accumulate) v += double(o[j]);
+      o[j] = float(v);
+    }
+  }
+}
+
 // The identity "pixel list" of a range: entry k names ray k.
 static __global__ __launch_bounds__(256) void k_ray_identity(uint32_t* list, uint32_t n) {
   const uint32_t gs = gridDim.x * blockDim.x;
@@ -212,6 +299,31 @@ hipError_t launch_gather_rays(const float4* pts, uint32_t n, int32_t kind, uint3
   const long long need = (n + 255u) / 256u, resident = (long long)(cus > 0 ? cus : 1) * 8;
   hipLaunchKernelGGL(k_gather_rays, dim3(uint32_t(need < resident ? need : resident)), dim3(256), 0, st, pts, n, int(kind),
                      seed, sample, out);
+  return hipGetLastError();
+}
+
+hipError_t launch_sh_accum(const WaveArgs& a, const RaySource& src, uint32_t nsamp, uint32_t sample_base, int bands,
+                           double* acc, int cus, hipStream_t st) {
+  if (a.npix == 0 || nsamp == 0) return hipSuccess;
+  if (!src.rays || !acc || src.kind != SRC_SPHERE || size_t(nsamp) * a.npix > a.slots) return hipErrorInvalidValue;
+  const long long need = (a.npix + 255u) / 256u, resident = (long long)(cus > 0 ? cus : 1) * 8;
+  const dim3 grid(uint32_t(need < resident ? need : resident)), block(256);
+  switch (bands) {
+    case 1: hipLaunchKernelGGL(k_sh_accum<1>, grid, block, 0, st, a.Lout, a.pixels, src, a.npix, nsamp, a.seed, sample_base, acc); break;
+    case 2: hipLaunchKernelGGL(k_sh_accum<2>, grid, block, 0, st, a.Lout, a.pixels, src, a.npix, nsamp, a.seed, sample_base, acc); break;
+    case 3: hipLaunchKernelGGL(k_sh_accum<3>, grid, block, 0, st, a.Lout, a.pixels, src, a.npix, nsamp, a.seed, sample_base, acc); break;
+    default: return hipErrorInvalidValue;   // a missing kernel is an error
+  }
+  return hipGetLastError();
+}
+
+hipError_t launch_sh_finalize(const double* acc, const uint32_t* pixels, uint32_t npix, int bands, float* out,
+                              int accumulate, int cus, hipStream_t st) {
+  if (npix == 0) return hipSuccess;
+  if (!acc || !pixels || !out || bands < 1 || bands > kShMaxBands) return hipErrorInvalidValue;
+  const long long need = (npix + 255u) / 256u, resident = (long long)(cus > 0 ? cus : 1) * 8;
+  hipLaunchKernelGGL(k_sh_finalize, dim3(uint32_t(need < resident ? need : resident)), dim3(256), 0, st, acc, pixels, npix,
+                     uint32_t(sh_floats(bands)), out, accumulate);
   return hipGetLastError();
 }
 #endif  // RTG_HOST_EMU

@@ -159,6 +159,16 @@ struct WavePlan {
   // launch_wavefront's `out` is the range's 3 floats per ray.  Not with
   // feat_acc, mom_acc, the path probes or an instrumented run.
   const RaySource* ray_src;
+  // SH mode (rt_gather_sh, ray_source.hip): non-null = the ray mode runs as
+  // ever under SRC_SPHERE and each batch's k_accum is followed by k_sh_accum
+  // over the same Lout entries; k_sh_finalize takes k_finalize's place and
+  // writes `sh_out`, the range's 3 * sh_bands^2 floats per point (no rgb sum is
+  // written: launch_wavefront's `out` is not read).  sh_acc[t] holds twin t's
+  // fp64 sums, coefficient-major over its listed points.  Only together with
+  // ray_src; not with feat_acc, mom_acc, the path probes or an instrumented run.
+  double* const* sh_acc;
+  float* sh_out;
+  int32_t sh_bands;
 };
 
 enum : uint32_t { EARLY_NEE = 1u, EARLY_NEXT = 2u };   // WaveArgs::early_miss

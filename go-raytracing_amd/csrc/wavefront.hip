@@ -1336,6 +1336,12 @@ static hipError_t run_batches(const WaveKernels& k, const DScene& sc, const DCam
           if ((e = launch_moment_accum(as[t].Lout, as[t].npix, sb, plan.mom_acc[t], cus, st)) != hipSuccess) return e;
           RTG_LAUNCHED("k_moment_accum", plan.max_depth, st);
         }
+        if (plan.sh_acc) {
+          if ((e = launch_sh_accum(as[t], *plan.ray_src, sb, sample_base, plan.sh_bands, plan.sh_acc[t], cus, st)) !=
+              hipSuccess)
+            return e;
+          RTG_LAUNCHED("k_sh_accum", plan.max_depth, st);
+        }
       }
   }
   return hipGetLastError();
@@ -1399,12 +1405,17 @@ hipError_t launch_wavefront(const DScene& sc, const DCamera& cam, const WaveArgs
   const bool mom = plan.mom_acc != nullptr;     // the frame, and the moments image plan.mom_out (moments.h)
   if (mom && (count || feat || !plan.mom_out)) return hipErrorInvalidValue;
   if (plan.ray_src && (count || feat || mom)) return hipErrorInvalidValue;   // ray mode: the plain render path only
+  const bool sh = plan.sh_acc != nullptr;       // rt_gather_sh: plan.sh_out in the rgb sums' place (ray_source.h)
+  if (sh && (!plan.ray_src || !plan.sh_out || plan.sh_bands < 1 || plan.sh_bands > kShMaxBands)) return hipErrorInvalidValue;
   for (int t = 0; t < nt; ++t) {
     if (feat) e = hipMemsetAsync(plan.feat_acc[t], 0, size_t(as[t].npix) * kFeatFloats * sizeof(double), sts[t]);
     else e = hipMemsetAsync(as[t].acc, 0, size_t(as[t].npix) * 3 * sizeof(double), sts[t]);
     if (e != hipSuccess) return e;
     if (mom && (e = hipMemsetAsync(plan.mom_acc[t], 0, size_t(as[t].npix) * kMomFloats * sizeof(double), sts[t])) !=
                    hipSuccess)
+      return e;
+    if (sh && (e = hipMemsetAsync(plan.sh_acc[t], 0, size_t(as[t].npix) * sh_floats(plan.sh_bands) * sizeof(double),
+                                  sts[t])) != hipSuccess)
       return e;
   }
   if (plan.max_depth > 0) {
@@ -1426,6 +1437,13 @@ hipError_t launch_wavefront(const DScene& sc, const DCamera& cam, const WaveArgs
     for (int t = 0; t < nt; ++t)
       if ((e = launch_feat_finalize(plan.feat_acc[t], as[t].pixels, as[t].npix, out, accumulate, plan.num_cus,
                                     sts[t])) != hipSuccess)
+        return e;
+    return hipGetLastError();
+  }
+  if (sh) {
+    for (int t = 0; t < nt; ++t)
+      if ((e = launch_sh_finalize(plan.sh_acc[t], as[t].pixels, as[t].npix, plan.sh_bands, plan.sh_out, accumulate,
+                                  plan.num_cus, sts[t])) != hipSuccess)
         return e;
     return hipGetLastError();
   }

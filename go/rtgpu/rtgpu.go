@@ -968,8 +968,55 @@ func (c *Ctx) Gather(pts []GatherPoint, source int32, p RayColorParams, rgb []fl
 	return st, c.check(rc)
 }
 
+// The largest band count GatherSH takes.
+const (
+	SHMaxBands int32 = 3 // RT_SH_MAX_BANDS
+)
+
+// GatherSHParams mirrors rt_gather_sh_params (GatherParams' layout).  Path
+// holds the words of a RayColorParams (56 B, 8-aligned); GatherSH fills it.
+//
+//rtgpu:mirror rt_gather_sh_params
+type GatherSHParams struct {
+	Path     [7]uint64 `c:"path"`
+	Bands    int32     `c:"bands"`
+	Reserved int32     `c:"reserved"`
+}
+
+// GatherSH is Gather under GatherSphere kept by direction (rt_gather_sh): a
+// light probe.  sh[(i*bands*bands+k)*3 + c] receives the sum over p.Samples
+// directions d on the sphere of the radiance along d times Y_k(d), the real
+// spherical-harmonic basis of Ramamoorthi & Hanrahan in the scene's axes, for
+// k < bands*bands (bands 1..3: 1, 4 or 9 coefficients per point).  The
+// projection coefficients are 4*pi/samples times the sums; the irradiance
+// about a unit normal n is the sum of A_l c_lm Y_lm(n) with A = pi, 2*pi/3,
+// pi/4.  p.Accumulate adds sh's previous values, so a probe is refined over
+// calls with a growing p.SampleOffset.  N is not read.  A point with a
+// non-finite position adds nothing and is counted in the stats.  Blocks.
+func (c *Ctx) GatherSH(pts []GatherPoint, bands int32, p RayColorParams, sh []float32) (RayColorStats, error) {
+	var st RayColorStats
+	if bands < 1 || bands > SHMaxBands {
+		return st, &Error{StatusInvalid, "SH bands outside 1 .. 3"}
+	}
+	if len(sh) < 3*int(bands*bands)*len(pts) {
+		return st, &Error{StatusInvalid, "coefficient buffer too small"}
+	}
+	if len(pts) == 0 {
+		return st, nil
+	}
+	var gp GatherSHParams
+	*(*RayColorParams)(unsafe.Pointer(&gp.Path)) = p
+	gp.Bands = bands
+	rc := C.rt_gather_sh(c.p, (*C.rt_gather_point)(unsafe.Pointer(&pts[0])), C.int64_t(len(pts)),
+		(*C.rt_gather_sh_params)(unsafe.Pointer(&gp)), (*C.float)(unsafe.Pointer(&sh[0])),
+		(*C.rt_ray_color_stats)(unsafe.Pointer(&st)))
+	return st, c.check(rc)
+}
+
 // Layout checks: each mirror is exactly as large as its C struct.
 var (
+	_ [unsafe.Sizeof(GatherSHParams{}) - uintptr(C.sizeof_rt_gather_sh_params)]byte
+	_ [uintptr(C.sizeof_rt_gather_sh_params) - unsafe.Sizeof(GatherSHParams{})]byte
 	_ [unsafe.Sizeof(GatherPoint{}) - uintptr(C.sizeof_rt_gather_point)]byte
 	_ [uintptr(C.sizeof_rt_gather_point) - unsafe.Sizeof(GatherPoint{})]byte
 	_ [unsafe.Sizeof(GatherParams{}) - uintptr(C.sizeof_rt_gather_params)]byte

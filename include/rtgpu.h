@@ -1000,8 +1000,8 @@ int rt_ray_color_device(rt_ctx* ctx, const rt_path_ray* rays_dev, int64_t n, con
  * for rt_gather_rays sample < 0.
  * Not offered (yet): next-event estimation at the gather point itself (direct
  * light reaches a point only through rays that hit an emitter, as for a camera
- * ray), SH projection of a probe, moments or adaptive sampling over points,
- * per-point source kinds.                                                     */
+ * ray), moments or adaptive sampling over points, per-point source kinds.
+ * (The projection of a probe onto spherical harmonics is rt_gather_sh, below.) */
 enum { RT_GATHER_RAY = 0, RT_GATHER_COSINE = 1, RT_GATHER_SPHERE = 2 };
 typedef struct rt_gather_point { float p[3]; uint32_t id; float n[3]; uint32_t reserved; } rt_gather_point; /* 32 B, rt_path_ray's layout */
 typedef struct rt_gather_params { rt_ray_color_params path; int32_t source; int32_t reserved; } rt_gather_params; /* 64 B */
@@ -1013,6 +1013,71 @@ int rt_gather_device(rt_ctx* ctx, const rt_gather_point* pts_dev, int64_t n, con
 /* probe: the ray sample `sample` of every point traces */
 int rt_gather_rays(rt_ctx* ctx, const rt_gather_point* pts, int64_t n, int32_t source, uint32_t seed, int32_t sample,
                    rt_path_ray* out);
+
+/* ---- SH projection of a probe: rt_gather over the sphere, kept by direction -
+ * Which light arrives at this point, from where?  A light probe is radiance as
+ * a function of direction, stored as a few spherical-harmonic coefficients
+ * (INTEGRATION.md §4).  rt_gather(RT_GATHER_SPHERE) folds a point's directions
+ * into one sum; this call keeps them apart: every sample's radiance is weighted
+ * with the SH basis at its own direction, on the device, so nothing per sample
+ * crosses the bus.
+ *
+ * Rays: the ray of sample s of point i is exactly rt_gather's under
+ * RT_GATHER_SPHERE: its key is path_key(seed, pts[i].id, sample_offset + s),
+ * its origin is p and its direction is d = random_unit_vector(key, 0,
+ * DOM_SOURCE, 0); n is not read.  Everything rt_gather and rt_ray_color
+ * document holds unchanged: volumes, next-event estimation along the path,
+ * lifted primitives and the long-tail kernel, the independence of the schedule
+ * options and of the cut of the array into ranges, the first device of a
+ * multi-device context, how device errors surface, n == 0 and the limit on n.
+ *
+ * Basis: with L the float radiance rayColorInternal(ray_{i,s}, max_depth) of
+ * that sample and (x, y, z) = d, in fp32 in the order written with no fused
+ * multiply-add (the real, all-positive convention of Ramamoorthi & Hanrahan
+ * 2001; the scene's axes as they are):
+ *   Y0 = 0.282095f
+ *   Y1 = 0.488603f*y       Y2 = 0.488603f*z       Y3 = 0.488603f*x
+ *   Y4 = 1.092548f*(x*y)   Y5 = 1.092548f*(y*z)   Y6 = 0.315392f*(3.0f*(z*z) - 1.0f)
+ *   Y7 = 1.092548f*(x*z)   Y8 = 0.546274f*(x*x - y*y)
+ * bands = b keeps Y0 .. Y(b*b-1): 1, 4 or 9 coefficients per point, and the
+ * coefficients of a smaller b are the first of a larger one, bit for bit.
+ *
+ * Result: sh[(i*b*b + k)*3 + c] = float(sum_s double(L_s.c) * double(Y_k(d_s))).
+ * The sum is fp64 in sample order across batches, rounded to float once per
+ * call; the product of two floats is exact in fp64.  accumulate != 0 adds
+ * double(sh's previous value) to the sum before that rounding, so a probe is
+ * refined over calls with growing sample_offset.  The sums are not scaled:
+ * the projection coefficients of the radiance are c_k = (4 pi / samples) * sh,
+ * and the irradiance about a unit normal n is
+ *   E(n) = sum_l A_l sum_m c_lm Y_lm(n),  A_0 = pi, A_1 = 2 pi / 3, A_2 = pi / 4
+ * (l = 0: k = 0; l = 1: k = 1..3; l = 2: k = 4..8), evaluated by the caller.
+ *
+ * A point with a non-finite component of p is invalid: it traces nothing and
+ * draws nothing, adds 0 to every coefficient (with accumulate it keeps its
+ * previous values), raises no device error, and is counted in
+ * stats->invalid_rays (host variant only).
+ *
+ * The equality that defines it: for every s < samples take the rays of
+ * rt_gather_rays(pts, RT_GATHER_SPHERE, seed, sample_offset + s) and
+ * rt_ray_color over them with samples = 1 and that offset; project those in
+ * fp64 by the formulas above, in order s, and round once: that is rt_gather_sh,
+ * bit for bit.
+ *
+ * RT_ERR_INVALID: everything rt_ray_color refuses, bands outside 1..3, a
+ * non-zero params->reserved, a point's reserved != 0 (host variant only).
+ * Not offered (yet): bands above 3, a cosine- or otherwise-weighted
+ * projection, irradiance evaluation on the device, moments per coefficient.   */
+enum { RT_SH_MAX_BANDS = 3 };
+typedef struct rt_gather_sh_params {
+  rt_ray_color_params path;   /* as rt_gather_params.path                         */
+  int32_t bands;              /* 1..3: bands*bands coefficients per point (1,4,9) */
+  int32_t reserved;           /* 0                                                */
+} rt_gather_sh_params;        /* 64 B, rt_gather_params' layout */
+
+int rt_gather_sh(rt_ctx* ctx, const rt_gather_point* pts, int64_t n, const rt_gather_sh_params* params,
+                 float* sh /* n * bands*bands * 3 */, rt_ray_color_stats* stats /* may be NULL */);
+int rt_gather_sh_device(rt_ctx* ctx, const rt_gather_point* pts_dev, int64_t n, const rt_gather_sh_params* params,
+                        float* sh_dev, void* hip_stream);
 
 #ifdef __cplusplus
 }
