@@ -285,6 +285,19 @@ def gather_sh_params(bands: int, samples: int, depth: int, seed: int = 1, sample
     return g
 
 
+class RtGatherSurfaceParams(C.Structure):
+    """rt_gather_surface_params (64 B, rt_gather_params' layout)."""
+    _fields_ = [("path", RtRayColorParams), ("reserved", C.c_int32 * 2)]
+
+
+def surface_params(samples: int, depth: int, seed: int = 1, sample_offset: int = 0, camera=None,
+                   accumulate: bool = False, **sky) -> RtGatherSurfaceParams:
+    """rt_gather_surface_params: the path fields of ray_color_params."""
+    g = RtGatherSurfaceParams()
+    g.path = ray_color_params(samples, depth, seed, sample_offset, camera, accumulate, **sky)
+    return g
+
+
 class RtWorkCounts(C.Structure):
     _fields_ = [(n, C.c_uint64) for n in ("samples", "rays", "shadow_rays", "node_visits", "sphere_tests",
                                           "quad_tests", "tri_tests", "plane_tests", "instance_visits",
@@ -427,6 +440,10 @@ def rtgpu() -> C.CDLL:
             lib.rt_gather_sh.argtypes = [P, C.POINTER(RtGatherPoint), C.c_int64, C.POINTER(RtGatherShParams),
                                          C.POINTER(C.c_float), C.POINTER(RtRayColorStats)]
             lib.rt_gather_sh_device.argtypes = [P, P, C.c_int64, C.POINTER(RtGatherShParams), P, P]
+        if hasattr(lib, "rt_gather_surface"):
+            lib.rt_gather_surface.argtypes = [P, C.POINTER(RtGatherPoint), C.c_int64, C.POINTER(RtGatherSurfaceParams),
+                                              C.POINTER(C.c_float), C.POINTER(RtRayColorStats)]
+            lib.rt_gather_surface_device.argtypes = [P, P, C.c_int64, C.POINTER(RtGatherSurfaceParams), P, P]
         _rtgpu = lib
     return _rtgpu
 
@@ -1182,6 +1199,34 @@ class Context:
         3 * bands^2 * n floats at sh_ptr, asynchronous on `stream`."""
         self._check(self._lib.rt_gather_sh_device(self._h, C.c_void_p(pts_ptr), n, C.byref(params), C.c_void_p(sh_ptr),
                                                   C.c_void_p(stream)))
+
+    # ---- next-event estimation at the gather point (rt_gather_surface)
+    def gather_surface(self, pts: np.ndarray, samples: int, depth: int, seed: int = 1, sample_offset: int = 0,
+                       camera=None, accum: Optional[np.ndarray] = None, **sky):
+        """rt_gather_surface: pts as for gather; every point is shaded as the
+        render's first diffuse vertex (white Lambertian, normal unit(n)): the
+        lights are sampled at the point and the scattered path goes on under
+        the light-hit rule.  Returns the (n, 3) float32 sums over `samples`
+        paths per point and the stats; pi * rgb / samples is the irradiance
+        as the render estimates it, depth = 1 the direct light alone.  The
+        rest as gather."""
+        pts = np.ascontiguousarray(pts, GATHER_POINT_DTYPE)
+        n = pts.shape[0]
+        p = surface_params(samples, depth, seed, sample_offset, camera, accum is not None, **sky)
+        if accum is None:
+            accum = np.zeros((n, 3), np.float32)
+        if accum.dtype != np.float32 or accum.size != 3 * n or not accum.flags["C_CONTIGUOUS"]:
+            raise ValueError("accum must be a contiguous float32 array of 3 floats per point")
+        st = RtRayColorStats()
+        self._check(self._lib.rt_gather_surface(self._h, pts.ctypes.data_as(C.POINTER(RtGatherPoint)), n, C.byref(p),
+                                                _f32p(accum), C.byref(st)))
+        return accum, st
+
+    def gather_surface_device(self, pts_ptr: int, n: int, params: RtGatherSurfaceParams, rgb_ptr: int, stream: int = 0):
+        """rt_gather_surface_device: n rt_gather_point at device address
+        pts_ptr -> 3 n floats at rgb_ptr, asynchronous on `stream`."""
+        self._check(self._lib.rt_gather_surface_device(self._h, C.c_void_p(pts_ptr), n, C.byref(params),
+                                                       C.c_void_p(rgb_ptr), C.c_void_p(stream)))
 
 
 # ---------------------------------------------------------------------------

@@ -2329,6 +2329,12 @@ int gather_sh_check(rt_ctx* ctx, int32_t bands, int32_t reserved) {
   return RT_OK;
 }
 
+// rt_gather_surface's own refusals (the rest are ray_color_check's).
+int gather_surface_check(rt_ctx* ctx, const int32_t (&reserved)[2]) {
+  if (reserved[0] != 0 || reserved[1] != 0) return set_err(ctx, RT_ERR_INVALID, "rt_gather_surface_params.reserved is not 0");
+  return RT_OK;
+}
+
 // source_ray's guard (ray_source.hip) for the host variant's count; fp32 in its order.
 bool gather_point_valid(const rt_gather_point& q, int32_t source) {
   if (!(std::isfinite(q.p[0]) && std::isfinite(q.p[1]) && std::isfinite(q.p[2]))) return false;
@@ -2485,6 +2491,42 @@ int rt_gather_sh_device(rt_ctx* ctx, const rt_gather_point* pts_dev, int64_t n, 
   if (rc || (rc = check_render_error(ctx, false)) || n == 0) return rc;
   return ray_color_device(ctx, dc, SRC_SPHERE, reinterpret_cast<const rt_path_ray*>(pts_dev), n, &params->path, sh_dev, st,
                           params->bands);
+}
+
+// ---- rt_gather_surface: the point is the path's first diffuse vertex ----------
+// (k_gather_source<SRC_SURFACE>, then run_batches' surface mode)
+
+static_assert(sizeof(rt_gather_surface_params) == sizeof(rt_gather_params) &&
+                  offsetof(rt_gather_surface_params, reserved) == offsetof(rt_gather_params, source),
+              "rt_gather_surface_params is rt_gather_params' layout");
+
+int rt_gather_surface(rt_ctx* ctx, const rt_gather_point* pts, int64_t n, const rt_gather_surface_params* params,
+                      float* rgb, rt_ray_color_stats* stats) {
+  if (!ctx || !pts || !params || !rgb) return RT_ERR_INVALID;
+  HIPCHK(hipSetDevice(ctx->device));
+  if (int rc = gather_surface_check(ctx, params->reserved)) return rc;
+  DCamera dc{};
+  int rc = ray_color_check(ctx, &params->path, n, dc);
+  if (rc) return rc;
+  uint64_t invalid = 0;
+  for (int64_t i = 0; i < n; ++i) {
+    if (pts[i].reserved != 0) return set_err(ctx, RT_ERR_INVALID, "a point's reserved word is not 0");
+    invalid += !gather_point_valid(pts[i], RT_GATHER_COSINE);
+  }
+  return ray_color_host(ctx, dc, SRC_SURFACE, pts, n, &params->path, rgb, stats, invalid);
+}
+
+int rt_gather_surface_device(rt_ctx* ctx, const rt_gather_point* pts_dev, int64_t n,
+                             const rt_gather_surface_params* params, float* rgb_dev, void* hip_stream) {
+  if (!ctx || !pts_dev || !params || !rgb_dev) return RT_ERR_INVALID;
+  HIPCHK(hipSetDevice(ctx->device));
+  hipStream_t st = hip_stream ? static_cast<hipStream_t>(hip_stream) : ctx->stream;
+  if (int rc = gather_surface_check(ctx, params->reserved)) return rc;
+  DCamera dc{};
+  int rc = ray_color_check(ctx, &params->path, n, dc);
+  if (rc || (rc = check_render_error(ctx, false)) || n == 0) return rc;
+  return ray_color_device(ctx, dc, SRC_SURFACE, reinterpret_cast<const rt_path_ray*>(pts_dev), n, &params->path, rgb_dev,
+                          st);
 }
 
 }  // extern "C"

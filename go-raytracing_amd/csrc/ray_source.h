@@ -12,8 +12,10 @@ namespace rtg {
 // a zero-initialised RaySource) is rt_ray_color: the record is the ray.  The
 // others are rt_gather's sources (1 + rtgpu.h's RT_GATHER_* value): the record
 // is a point and its normal, and the direction is a function of the sample's
-// path key.
-enum : int32_t { SRC_CALLER = 0, SRC_RAY = 1, SRC_COSINE = 2, SRC_SPHERE = 3 };
+// path key.  SRC_SURFACE is rt_gather_surface: the record is a point and its
+// normal and no ray is made of it; stream 0 carries the vertex (p, unit(n)) and
+// bounce 0 shades it without tracing (run_batches' surface mode).
+enum : int32_t { SRC_CALLER = 0, SRC_RAY = 1, SRC_COSINE = 2, SRC_SPHERE = 3, SRC_SURFACE = 4 };
 
 // The rays of one rt_ray_color / rt_gather range.  A record is two float4
 // (rt_path_ray: origin.xyz, id; direction.xyz, reserved; rt_gather_point has
@@ -29,7 +31,8 @@ struct RaySource {
 // Slot i of a batch of `nslots` (= samples * a.npix) takes record
 // a.pixels[i % a.npix] at sample sample_base + i / a.npix: Lout[i] = 0, and,
 // for a record whose ray is valid, stream 0 gets (origin, slot), (direction,
-// key), (1, 1, 1, state(a.max_depth, bounce 0, emitters count)).  The valid
+// key), (1, 1, 1, state(a.max_depth, bounce 0, emitters count)); under
+// SRC_SURFACE the second is (unit normal, key).  The valid
 // rays are dense in stream 0; a.counts[CNT_STREAM0], which must be 0 when the
 // kernel starts (k_set_counts), ends as their number.
 hipError_t launch_ray_source(const WaveArgs& a, const RaySource& src, uint32_t nslots, uint32_t sample_base, int cus,

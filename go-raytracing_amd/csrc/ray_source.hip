@@ -117,6 +117,14 @@ __device__ __forceinline__ void ray_source_chunks(const WaveArgs& a, const RaySo
         d4 = rsrc::ldnt(&src.rays[2u * size_t(ray) + 1u]);
         if (kKind == SRC_CALLER) {
           valid = rsrc::valid_ray(o4, d4);
+        } else if (kKind == SRC_SURFACE) {
+          // no ray and no draw: the record stays a vertex, (p, unit(n)), under
+          // the guard of the sources that read the normal (source_ray's SRC_RAY)
+          V3 ro, rd;
+          key = path_key(a.seed, __float_as_uint(o4.w), sample_base + i / a.npix);
+          valid = source_ray(SRC_RAY, o4, d4, key, ro, rd);
+          if (valid) rd = unit(rd);
+          d4 = make_float4(rd.x, rd.y, rd.z, d4.w);
         } else {   // the ray's origin is the point; its direction takes the normal's place
           V3 ro, rd;
           key = path_key(a.seed, __float_as_uint(o4.w), sample_base + i / a.npix);
@@ -151,10 +159,13 @@ static __global__ __launch_bounds__(256) void k_ray_source(WaveArgs a, RaySource
   ray_source_chunks<SRC_CALLER>(a, src, nslots, sample_base, blockDim.x, gridDim.x);
 }
 
-// rt_gather's sources: one kernel per kind (SRC_RAY, SRC_COSINE, SRC_SPHERE).
+// rt_gather's sources: one kernel per kind (SRC_RAY, SRC_COSINE, SRC_SPHERE),
+// and rt_gather_surface's (SRC_SURFACE): stream 0 gets (p, slot), (unit(n),
+// key), (1, 1, 1, state) for k_shade's surface instantiation, which runs in
+// bounce 0's k_extend's place (wavefront.hip, AT_SURFACE).
 template <int kKind>
 static __global__ __launch_bounds__(256) void k_gather_source(WaveArgs a, RaySource src, uint32_t nslots, uint32_t sample_base) {
-  static_assert(kKind == SRC_RAY || kKind == SRC_COSINE || kKind == SRC_SPHERE, "a gather source");
+  static_assert(kKind == SRC_RAY || kKind == SRC_COSINE || kKind == SRC_SPHERE || kKind == SRC_SURFACE, "a gather source");
   ray_source_chunks<kKind>(a, src, nslots, sample_base, blockDim.x, gridDim.x);
 }
 
@@ -287,6 +298,7 @@ hipError_t launch_ray_source(const WaveArgs& a, const RaySource& src, uint32_t n
     case SRC_RAY: hipLaunchKernelGGL(k_gather_source<SRC_RAY>, grid, block, 0, st, a, src, nslots, sample_base); break;
     case SRC_COSINE: hipLaunchKernelGGL(k_gather_source<SRC_COSINE>, grid, block, 0, st, a, src, nslots, sample_base); break;
     case SRC_SPHERE: hipLaunchKernelGGL(k_gather_source<SRC_SPHERE>, grid, block, 0, st, a, src, nslots, sample_base); break;
+    case SRC_SURFACE: hipLaunchKernelGGL(k_gather_source<SRC_SURFACE>, grid, block, 0, st, a, src, nslots, sample_base); break;
     default: return hipErrorInvalidValue;   // a missing kernel is an error
   }
   return hipGetLastError();

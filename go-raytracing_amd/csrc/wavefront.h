@@ -158,6 +158,11 @@ struct WavePlan {
   // the twins' "pixel lists" hold ray indices into ray_src->rays, and
   // launch_wavefront's `out` is the range's 3 floats per ray.  Not with
   // feat_acc, mom_acc, the path probes or an instrumented run.
+  // Surface mode (rt_gather_surface), carried by ray_src->kind == SRC_SURFACE:
+  // stream 0 holds given vertices (point, unit normal), bounce 0 launches no
+  // k_extend and k_shade's surface instantiation in k_shade's place, then
+  // k_shadow / k_nee_apply as ever; from bounce 1 on it is the ray mode.  Not
+  // with sh_acc either.
   const RaySource* ray_src;
   // SH mode (rt_gather_sh, ray_source.hip): non-null = the ray mode runs as
   // ever under SRC_SPHERE and each batch's k_accum is followed by k_sh_accum

@@ -366,7 +366,14 @@ __device__ __forceinline__ uint32_t shade_claim(uint32_t* ctr, uint32_t nchunks,
 //   (NEE rays: flags, da / tmax_a / ca, dh / ch)
 //   kShadeL: the shading kind (SHADE_*), | SHADE_LIFT in the variant that also
 //   tests the world primitives lifted out of the world BVH (DScene.prim_recs)
-template <bool kCount, bool kEnvIS, int kShadeL, bool kFirst>
+//   kMode (AT_*): AT_STREAM a later bounce, AT_CAMERA bounce 0 of a render (the
+//   radiance starts here), AT_SURFACE rt_gather_surface's bounce 0: no ray was
+//   traced and `h` is not read; the vertex is given, ro its point and rd its
+//   unit normal, a front-face hit of a Lambertian of SolidColor(1, 1, 1).  It
+//   enters the Lambertian branch below with att = 1 and shares everything
+//   from there on: the scatter draw, the NEE set-up, the next state.
+enum : int { AT_STREAM = 0, AT_CAMERA = 1, AT_SURFACE = 2 };
+template <bool kCount, bool kEnvIS, int kShadeL, int kMode>
 __device__ __forceinline__ void shade_path(const DScene& sc, const DCamera& cam, const WaveArgs& a, const DVolRec* vrecs,
                                            const float4 h, const V3 ro, const V3 rd, const V3 beta, const uint32_t key,
                                            const uint32_t slot, const int dleft, const uint32_t bounce, const bool allow,
@@ -375,6 +382,7 @@ __device__ __forceinline__ void shade_path(const DScene& sc, const DCamera& cam,
                                            bool& lout_set, Cnt& cnt) {
   constexpr int kShade = kShadeL & SHADE_KIND_MASK;
   constexpr bool kLift = (kShadeL & SHADE_LIFT) != 0;
+  constexpr bool kFirst = kMode == AT_CAMERA, kSurf = kMode == AT_SURFACE;
   // L += beta * e on the path's radiance in Lout[slot] (camera.go:466, :481);
   // adding an exact zero (black background) leaves L unchanged, so it is
   // skipped.  At bounce 0 the radiance starts at 0 here (0 + beta * e).
@@ -390,18 +398,18 @@ __device__ __forceinline__ void shade_path(const DScene& sc, const DCamera& cam,
   uint32_t kh = asu(h.y);
   float ht = h.x;
   int hinst = int(asu(h.z));
-  if (kShade == SHADE_VOL) {
+  if (kShade == SHADE_VOL && !kSurf) {
     int hrefpos = int(asu(h.w));
     lifted_volumes<kCount>(sc, ro, rd, key, bounce, kh, ht, hinst, hrefpos, cnt, vrecs);
   }
-  if (kLift) {
+  if (kLift && !kSurf) {
     int hrefpos = int(asu(h.w));
     lifted_prims<kCount>(sc, ro, rd, time, kh, ht, hinst, hrefpos, cnt);
   }
 #ifdef RTG_GUARD
-  if (kh == 0xFFFFFFFFu) rtg_guard_note(50, slot, bounce);   // hit record never written by k_extend
+  if (!kSurf && kh == 0xFFFFFFFFu) rtg_guard_note(50, slot, bounce);   // hit record never written by k_extend
 #endif
-  if (kh == 0u) {                                            // miss (camera.go:451-466)
+  if (!kSurf && kh == 0u) {                                  // miss (camera.go:451-466)
     V3 bg;
     if (sc.env.valid) {
       if (cam.phantom && dleft == cam.cam_max_depth) bg = mk(0.0f, 0.0f, 0.0f);
@@ -418,19 +426,25 @@ __device__ __forceinline__ void shade_path(const DScene& sc, const DCamera& cam,
     Best b{};
     b.t = ht; b.kind = int(kh >> 28); b.idx = int(kh & 0x0FFFFFFFu); b.inst = hinst;
     b.refpos = 0; b.primpos = 0;
-    Rec rec = make_record<kShade == SHADE_FULL>(sc, b, ro, rd, time);
+    Rec rec;
+    if constexpr (kSurf) {
+      rec.P = ro; rec.N = rd; rec.front = true; rec.mat = 0; rec.u = 0.0f; rec.v = 0.0f;
+    } else {
+      rec = make_record<kShade == SHADE_FULL>(sc, b, ro, rd, time);
+    }
     P = rec.P;
-    const DMaterial& m = sc.materials[GIX(rec.mat, sc.num_materials, 42)];
-    if (kCount) cnt.mat++;
+    const DMaterial& m = sc.materials[kSurf ? 0 : GIX(rec.mat, sc.num_materials, 42)];   // (AT_SURFACE: not read)
+    if (kCount && !kSurf) cnt.mat++;
     V3 att = mk(0.0f, 0.0f, 0.0f);
     bool scat = true, use_mis = false;
-    if (m.kind == 4) {                                        // DiffuseLight
+    if (!kSurf && m.kind == 4) {                              // DiffuseLight
       if (allow) add_L(tex_value<kShade == SHADE_FULL>(sc, m.tex, rec.u, rec.v, rec.P));
       scat = false;
-    } else if (m.kind == 1) {                                 // Lambertian material.go:57-68
+    } else if (kSurf || m.kind == 1) {                        // Lambertian material.go:57-68
       sd = add(rec.N, random_unit_vector(key, bounce, DOM_SCATTER, 0));
       if (near_zero(sd)) sd = rec.N;
-      att = tex_value<kShade == SHADE_FULL>(sc, m.tex, rec.u, rec.v, rec.P);
+      if constexpr (kSurf) att = mk(1.0f, 1.0f, 1.0f);
+      else att = tex_value<kShade == SHADE_FULL>(sc, m.tex, rec.u, rec.v, rec.P);
       use_mis = sc.num_lights > 0;
     } else if (kShade == SHADE_LEAN) {
       scat = false;                                           // unreachable: no such material
@@ -621,9 +635,13 @@ constexpr int kShadeFullWaves = 4, kShadeLeanWaves = 7, kShadeMatWaves = 7, kSha
   (((kShadeL) & SHADE_KIND_MASK) == SHADE_FULL ? kShadeFullWaves                 \
    : ((kShadeL) & SHADE_KIND_MASK) == SHADE_MAT ? kShadeMatWaves                 \
    : ((kShadeL) & SHADE_KIND_MASK) == SHADE_VOL ? kShadeVolWaves : kShadeLeanWaves)
-// kFirst: bounce 0 — the path is the slot's camera ray (no stream to read)
-// and this kernel initialises the slot's radiance in Lout.
-template <bool kCount, bool kEnvIS, int kShadeL, bool kFirst>
+// kMode (AT_*): AT_CAMERA is bounce 0 of a render — the path is the slot's
+// camera ray (no stream to read) and this kernel initialises the slot's
+// radiance in Lout.  AT_SURFACE is bounce 0 of rt_gather_surface: no k_extend
+// ran; stream 0 holds (point, slot), (unit normal, key), (1, 1, 1, state) as
+// the source kernel wrote them, read like a later bounce's stream, and no hit
+// record is read (shade_path).
+template <bool kCount, bool kEnvIS, int kShadeL, int kMode>
 static __global__ __launch_bounds__(256, SHADE_WAVES(kShadeL)) void k_shade(DScene scg, DCamera cam, WaveArgs a, PathStream cs,
                                                const uint32_t* count, PathStream ns, uint32_t* ncount,
                                                uint32_t* jcount, uint32_t sample_base, uint32_t launch_bounce) {
@@ -636,6 +654,7 @@ static __global__ __launch_bounds__(256, SHADE_WAVES(kShadeL)) void k_shade(DSce
   extern __shared__ char s_dyn[];   // shade_lds_bytes(sc) per block (all records 16-B aligned, multiples of 16 B)
 #endif
   constexpr int kShade = kShadeL & SHADE_KIND_MASK;
+  constexpr bool kFirst = kMode == AT_CAMERA, kSurf = kMode == AT_SURFACE;
   // WaveArgs::early_miss is read only by the variants of scenes with lifted
   // world primitives, the only ones the host sets it for (early_miss_eligible):
   // every other variant is compiled without a trace of it
@@ -698,7 +717,7 @@ static __global__ __launch_bounds__(256, SHADE_WAVES(kShadeL)) void k_shade(DSce
       // a back entry was never traced: its ray misses the world box, and its
       // hit record is the miss k_extend would have stored for it (store_hit)
       const uint32_t ii = GIX(bchunk ? a.slots - nb + i : i, a.slots, 41);
-      const float4 h = bchunk ? make_float4(__builtin_inff(), 0.0f, asf(0xFFFFFFFFu), 0.0f) : ldnt(&a.hit[ii]);
+      const float4 h = (bchunk || kSurf) ? make_float4(__builtin_inff(), 0.0f, asf(0xFFFFFFFFu), 0.0f) : ldnt(&a.hit[ii]);
       // the block's next chunk, claimed beside the hit load and published by
       // the next iteration's barrier: the claim's round trip no longer holds
       // every wave of the block there
@@ -732,7 +751,7 @@ static __global__ __launch_bounds__(256, SHADE_WAVES(kShadeL)) void k_shade(DSce
         rd = mk(d4.x, d4.y, d4.z);
         beta = mk(b4.x, b4.y, b4.z);
       }
-      shade_path<kCount, kEnvIS, kShadeL, kFirst>(sc, cam, a, vrecs, h, ro, rd, beta, key, slot, dleft, bounce, allow, cont,
+      shade_path<kCount, kEnvIS, kShadeL, kMode>(sc, cam, a, vrecs, h, ro, rd, beta, key, slot, dleft, bounce, allow, cont,
                                                  want_shadow, flags, nstate, tmax_a, P, sd, nbeta, ca, ch, da, dh,
                                                  lout_set, cnt);
     }
@@ -883,7 +902,7 @@ static __global__ __launch_bounds__(256, kTailWaves) void k_tail(DScene scg, DCa
       uint32_t flags = 0, nstate = 0;
       float tmax_a = 0.0f;
       V3 P = mk(0.0f, 0.0f, 0.0f), sd = P, nbeta = P, ca = P, ch = P, da = P, dh = P;
-      shade_path<false, false, kShadeL, false>(sc, cam, a, sc.vol_recs, h, ro, rd, beta, key, slot, int(st & 0xFFFFu),
+      shade_path<false, false, kShadeL, AT_STREAM>(sc, cam, a, sc.vol_recs, h, ro, rd, beta, key, slot, int(st & 0xFFFFu),
                                               (st >> 16) & 0x7FFFu, (st >> 31) != 0u, cont, want_shadow, flags, nstate,
                                               tmax_a, P, sd, nbeta, ca, ch, da, dh, lout_set, cnt);
       if (cont) {   // the next bounce of the same path (k_shade's survivor record)
@@ -1131,6 +1150,7 @@ using TailFn = void (*)(DScene, DCamera, WaveArgs, PathStream, const uint32_t*, 
 struct WaveKernels {
   ExtendFn extend0, extend;   // bounce 0 (camera rays), later bounces
   ShadeFn shade0, shade;
+  ShadeFn surface;            // bounce 0 of rt_gather_surface (AT_SURFACE); null in the counting variants
   ShadowFn shadow;
   NeeApplyFn nee_apply;
   TailFn tail;                // null in the counting variants: they hand nothing to k_tail
@@ -1140,8 +1160,10 @@ template <int STACK, bool C, bool V, bool E, int S, bool Q, bool W>
 static WaveKernels kernels_for() {
   TailFn tail = nullptr;
   if constexpr (!C) tail = k_tail<STACK, V, S, Q, W>;
-  return {k_extend<STACK, C, V, true, Q, W>, k_extend<STACK, C, V, false, Q, W>, k_shade<C, E, S, true>,
-          k_shade<C, E, S, false>, k_shadow<STACK, C, V, E, Q, W>, k_nee_apply<E>, tail, C};
+  ShadeFn surface = nullptr;
+  if constexpr (!C) surface = k_shade<C, E, S, AT_SURFACE>;
+  return {k_extend<STACK, C, V, true, Q, W>, k_extend<STACK, C, V, false, Q, W>, k_shade<C, E, S, AT_CAMERA>,
+          k_shade<C, E, S, AT_STREAM>, surface, k_shadow<STACK, C, V, E, Q, W>, k_nee_apply<E>, tail, C};
 }
 
 // The render's work is split into twins (WavePlan::num_twins, 1 or 2):
@@ -1163,7 +1185,15 @@ static hipError_t run_batches(const WaveKernels& k, const DScene& sc, const DCam
   // ray mode (WavePlan::ray_src): bounce 0 reads stream 0 like any later bounce
   const bool ray = plan.ray_src != nullptr;
   const ExtendFn extend_first = ray ? k.extend : k.extend0;
-  const ShadeFn shade_first = ray ? k.shade : k.shade0;
+  // surface mode (RaySource::kind SRC_SURFACE): stream 0 holds given vertices,
+  // not rays.  Bounce 0 has no k_extend: k.surface shades the vertices, then
+  // k_shadow and k_nee_apply as ever; from bounce 1 on nothing differs.  What
+  // bounce 0's k_extend would have zeroed (the next stream's count, parity 0's
+  // NEE job count and claim counters, k_shade's chunk counters) k_set_counts
+  // has zeroed for the batch, and nothing has touched them since.
+  const bool surface = ray && plan.ray_src->kind == SRC_SURFACE;
+  if (surface && k.surface == nullptr) return hipErrorInvalidValue;   // a missing kernel is an error
+  const ShadeFn shade_first = surface ? k.surface : ray ? k.shade : k.shade0;
   hipError_t e;
   for (uint32_t s0 = 0; s0 < plan.spp; s0 += plan.samples_per_batch) {
     const uint32_t sb = plan.spp - s0 < plan.samples_per_batch ? plan.spp - s0 : plan.samples_per_batch;
@@ -1240,11 +1270,13 @@ static hipError_t run_batches(const WaveKernels& k, const DScene& sc, const DCam
         if ((e = hipMemsetAsync(a.hit, 0xFF, size_t(a.slots) * sizeof(float4), st)) != hipSuccess) return e;
 #endif
         // bounce 0 regenerates the camera rays (no stream; in ray mode it reads s[0] too), later bounces read s[c]
-        if ((e = mark_begin(plan, uint8_t(KC_EXTEND | (t << KC_TWIN_SHIFT)), st)) != hipSuccess) return e;
-        hipLaunchKernelGGL(b == 0 ? extend_first : k.extend, dim3(b == 0 ? gext0[t] : gext[t]), dim3(256), 0, st, sc, cam, a,
-                           a.s[c], cnt_stream[c], cnt_stream[nx], cnt_sh, fetch_sh, fetch_ext, sample_base);
-        if ((e = mark_end(plan, st)) != hipSuccess) return e;
-        RTG_LAUNCHED("k_extend", b, st);
+        if (!(surface && b == 0)) {
+          if ((e = mark_begin(plan, uint8_t(KC_EXTEND | (t << KC_TWIN_SHIFT)), st)) != hipSuccess) return e;
+          hipLaunchKernelGGL(b == 0 ? extend_first : k.extend, dim3(b == 0 ? gext0[t] : gext[t]), dim3(256), 0, st, sc, cam,
+                             a, a.s[c], cnt_stream[c], cnt_stream[nx], cnt_sh, fetch_sh, fetch_ext, sample_base);
+          if ((e = mark_end(plan, st)) != hipSuccess) return e;
+          RTG_LAUNCHED("k_extend", b, st);
+        }
         // k_shade b waits for k_nee_apply b - 1
         if (ovl && b > 0 && (e = hipStreamWaitEvent(st, plan.ev_nee[t], 0)) != hipSuccess) return e;
         if ((e = mark_begin(plan, uint8_t(KC_SHADE | (t << KC_TWIN_SHIFT)), st)) != hipSuccess) return e;
@@ -1406,7 +1438,7 @@ hipError_t launch_wavefront(const DScene& sc, const DCamera& cam, const WaveArgs
   if (mom && (count || feat || !plan.mom_out)) return hipErrorInvalidValue;
   if (plan.ray_src && (count || feat || mom)) return hipErrorInvalidValue;   // ray mode: the plain render path only
   const bool sh = plan.sh_acc != nullptr;       // rt_gather_sh: plan.sh_out in the rgb sums' place (ray_source.h)
-  if (sh && (!plan.ray_src || !plan.sh_out || plan.sh_bands < 1 || plan.sh_bands > kShMaxBands)) return hipErrorInvalidValue;
+  if (sh && (!plan.ray_src || plan.ray_src->kind == SRC_SURFACE || !plan.sh_out || plan.sh_bands < 1 || plan.sh_bands > kShMaxBands)) return hipErrorInvalidValue;
   for (int t = 0; t < nt; ++t) {
     if (feat) e = hipMemsetAsync(plan.feat_acc[t], 0, size_t(as[t].npix) * kFeatFloats * sizeof(double), sts[t]);
     else e = hipMemsetAsync(as[t].acc, 0, size_t(as[t].npix) * 3 * sizeof(double), sts[t]);

@@ -998,9 +998,11 @@ int rt_ray_color_device(rt_ctx* ctx, const rt_path_ray* rays_dev, int64_t n, con
  * RT_ERR_INVALID: everything rt_ray_color refuses, a source outside 0..2, a
  * non-zero params->reserved, a point's reserved != 0 (host variant only), and
  * for rt_gather_rays sample < 0.
- * Not offered (yet): next-event estimation at the gather point itself (direct
- * light reaches a point only through rays that hit an emitter, as for a camera
- * ray), moments or adaptive sampling over points, per-point source kinds.
+ * Not offered by this call: next-event estimation at the gather point itself
+ * (direct light reaches a point only through rays that hit an emitter, as for
+ * a camera ray; rt_gather_surface, below, samples the lights at the point as
+ * the render does at a diffuse hit).  Not offered (yet): moments or adaptive
+ * sampling over points, per-point source kinds.
  * (The projection of a probe onto spherical harmonics is rt_gather_sh, below.) */
 enum { RT_GATHER_RAY = 0, RT_GATHER_COSINE = 1, RT_GATHER_SPHERE = 2 };
 typedef struct rt_gather_point { float p[3]; uint32_t id; float n[3]; uint32_t reserved; } rt_gather_point; /* 32 B, rt_path_ray's layout */
@@ -1078,6 +1080,90 @@ int rt_gather_sh(rt_ctx* ctx, const rt_gather_point* pts, int64_t n, const rt_ga
                  float* sh /* n * bands*bands * 3 */, rt_ray_color_stats* stats /* may be NULL */);
 int rt_gather_sh_device(rt_ctx* ctx, const rt_gather_point* pts_dev, int64_t n, const rt_gather_sh_params* params,
                         float* sh_dev, void* hip_stream);
+
+/* ---- Surface gathers: next-event estimation at the gather point ------------
+ * What does the render put on this texel?  (Irradiance and lightmap bakes
+ * under small lights: INTEGRATION.md §4.)  rt_gather(RT_GATHER_COSINE) starts
+ * a plain ray at every point, so direct light reaches a texel only through
+ * rays that happen to hit an emitter.  This call treats the point as the
+ * render's own first diffuse vertex instead: it samples the lights at the
+ * point (sampleLightMIS, camera.go:502-678) and continues the scattered path
+ * under the light-hit rule.
+ *
+ * Sample s of point i runs under key = path_key(seed, pts[i].id,
+ * sample_offset + s).  It is the path rayColorInternal(., max_depth) continues
+ * after its world.Hit at bounce 0 returned a front-face hit with P = p,
+ * Normal = nh = unit(n), and a Lambertian of SolidColor(1,1,1).  From there,
+ * in fp32 in the order written with no fused multiply-add:
+ *   Emission        none is added at the vertex.
+ *   Scattered ray   origin p, direction sd = nh + random_unit_vector(key,
+ *                   bounce 0, DOM_SCATTER = 1, index 0), and sd = nh where
+ *                   near_zero(sd): Lambertian.Scatter with the path's own
+ *                   scatter draw of bounce 0 (not DOM_SOURCE).  The
+ *                   attenuation is (1,1,1).
+ *   NEE             when the scene has lights: the render's set-up at bounce 0
+ *                   with rec.P = p, rec.N = nh, att = 1: the light select at
+ *                   (0, DOM_NEE, 0), sampleHDRILight when the environment is
+ *                   importance-sampled, sampleAreaLight with its cuts (cos <= 0,
+ *                   cosLight < 0.001), the weight pdfL / (pdfL + pdfB), the
+ *                   factor num_lights, the clamp at 20 and the shadow-ray end
+ *                   min(dist - 0.001, dist * (1 - 2^-20)); lifted volumes and
+ *                   lifted world primitives clear a shadow ray as in a render.
+ *   Continuation    the path goes on at bounce 1 with depth_left =
+ *                   max_depth - 1 and, by the light-hit rule, counts an emitter
+ *                   it hits only when the scene has no lights.  max_depth = 1
+ *                   is therefore a direct-only bake; with no lights in the
+ *                   scene the call traces what RT_GATHER_COSINE traces, from
+ *                   another RNG address.
+ * Result: rgb[3*i .. 3*i+2] is the sum of those path radiances over
+ * path.samples samples.  pi * rgb / samples is the radiosity-consistent
+ * irradiance at the point as the render estimates it.
+ *
+ * How it differs from RT_GATHER_COSINE: this is the reference's estimator as
+ * written.  With lights present a light sample adds emission * cos / pdfL
+ * (no 1/pi of the Lambertian BRDF) weighted by pdfL / (pdfL + pdfB) and clamped
+ * at 20, and a scattered ray that then hits an emitter adds nothing, so its
+ * expectation differs from COSINE's unbiased one: in direct light by about
+ * pi * weight, brighter wherever the weight is near 1 (a small or far light).
+ * It equals the rendered radiance of a white Lambertian texel: what rt_render
+ * shows of the same wall.
+ *
+ * The equality that defines it: take any rt_path_ray r whose closest hit is a
+ * front or back face of a Lambertian SolidColor(1,1,1) quad with an
+ * axis-aligned normal, no lifted volume entered before that hit.  Take t and n
+ * from rt_trace_rays(r, tmin = 0.001f, tmax = +inf) and P = o + d*t per
+ * component in fp32 (the product rounded, then the sum).  Then
+ * rt_gather_surface({P, r.id, n}, params) equals rt_ray_color(r, params.path),
+ * all bytes, under every node format, volume placement, RT_OPT_LIFT_PRIMS
+ * setting and schedule option.
+ *
+ * Everything else is rt_gather's rule, unchanged: the fp64 in-order per-point
+ * sum rounded once, accumulate, the cut of the array into ranges, the
+ * independence of RT_OPT_BATCH_SLOTS, RT_OPT_STREAMS, RT_OPT_MAX_BLOCKS,
+ * RT_OPT_TAIL, RT_OPT_OVERLAP and RT_OPT_EARLY_MISS, volumes in both
+ * placements, the scattered ray's time from the key's camera draw 2 (shadow
+ * rays run at time 0), the first device of a multi-device context, how errors
+ * surface, n <= 2^31 - 1 and n == 0.
+ *
+ * A point is invalid by RT_GATHER_COSINE's rule: a non-finite component of p
+ * or n, or an fp32 length of n that is 0 or not finite.  It draws nothing,
+ * adds (0,0,0), and is counted in stats->invalid_rays (host variant only).
+ *
+ * RT_ERR_INVALID: everything rt_ray_color refuses, a non-zero
+ * params->reserved[k], a point's reserved != 0 (host variant only).
+ * Not offered (yet): a surface albedo or a BSDF other than white Lambertian
+ * at the point, an SH or moments variant, a probe for the NEE records,
+ * unbiased MIS at the first vertex (a departure from the reference), dealing
+ * points over several devices.                                              */
+typedef struct rt_gather_surface_params {
+  rt_ray_color_params path;   /* as rt_gather_params.path */
+  int32_t reserved[2];        /* 0                        */
+} rt_gather_surface_params;   /* 64 B, rt_gather_params' layout */
+
+int rt_gather_surface(rt_ctx* ctx, const rt_gather_point* pts, int64_t n, const rt_gather_surface_params* params,
+                      float* rgb, rt_ray_color_stats* stats /* may be NULL */);
+int rt_gather_surface_device(rt_ctx* ctx, const rt_gather_point* pts_dev, int64_t n,
+                             const rt_gather_surface_params* params, float* rgb_dev, void* hip_stream);
 
 #ifdef __cplusplus
 }
